@@ -6,14 +6,22 @@ One step = one batch through the whole hot path, device resident:
   -> (N > 1) one RCCL all_gather of the padded detections over xGMI.
 
 Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--global-batch B]
+                       [--dump-outputs DIR] [--full]
 --gpus N > 1 starts N rank processes by itself (one per GPU, before any GPU
 call in the parent); a launch under torch.distributed.run (WORLD_SIZE set) is
 used as is. Images are sharded by rank (weak scaling: 32 images per GPU per
 step; --global-batch B: strong scaling, B images per step split over the ranks,
 "scaling": "strong").
 
-Prints ONE JSON line (rank 0) with images/s for the whole job, p50 step
-latency, the dominant kernel's roofline, and the CPU-oracle baseline.
+Prints ONE JSON line (rank 0) with images/s for the whole job (``value``), the
+time of one timed step (``ms_per_step``) and the p50 per-batch latency in the
+timed loop. A plain run does nothing else: set up, W warm-up steps, K timed
+steps, the result line. ``--full`` adds the legs that take runs of their own and
+their keys: the unloaded latency, the image-in variant, the dominant kernel's
+roofline and per-op gap table, the fp16 and the pipelined plans, and the
+CPU-oracle baseline. ``--dump-outputs DIR`` writes what the timed path returned
+in its last timed step (dets, keep_rows, keep_counts) as DIR/<name>.npy; the
+inputs are seeded, so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -110,6 +118,14 @@ def parse(argv=None):
                          "value_pipelined / ms_per_step_pipelined / p50_ms_pipelined")
     ap.add_argument("--round", default=None,
                     help="profiles/<round>/traffic.json for roofline.traffic (default: the newest round that has one)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs beside the headline figure: unloaded latency (--latency-steps), "
+                         "image-in (--image-in-steps), roofline / per-op gap table (--roofline-steps, "
+                         "YCX_BENCH_KERNELS), the fp16 and pipelined plans (--fp16-steps, --pipelined-steps) and "
+                         "the CPU baseline (--cpu-seconds); without it those options are not used")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write the last timed step's outputs (dets [n, max_det, 7], keep_rows [n, max_det], "
+                         "keep_counts [n]; gathered over the ranks at N > 1) as DIR/<name>.npy, float32 / float64")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher check without a GPU: every rank joins a gloo process group, all-gathers "
                          "fabricated padded detections and rank 0 prints one JSON line (no GPU legs)")
@@ -580,7 +596,8 @@ def dry_run(args, world, rank):
 def timed_leg(args, det, mode, dist_on, gather, lat_ev, steps=None, latency_steps=None):
     """W untimed warm-up steps, then exactly ``steps`` timed steps between a barrier +
     device synchronise on both sides (host wall clock), then the unloaded latency leg.
-    Returns (elapsed s, loaded per-batch latencies ms, unloaded latencies ms, last kc)."""
+    Returns (elapsed s, loaded per-batch latencies ms, unloaded latencies ms, last kc, and
+    the last timed step's (dets, keep, kc) copied to the host, None unless --dump-outputs)."""
     from ycx.dist import gather_detections
     steps = args.steps if steps is None else steps
     latency_steps = args.latency_steps if latency_steps is None else latency_steps
@@ -591,13 +608,13 @@ def timed_leg(args, det, mode, dist_on, gather, lat_ev, steps=None, latency_step
         if mode == "concurrent":  # the collective on the batch's own stream, issued in batch order on every rank
             dets, keep, kc, done = det.submit(timing=timing, then=gather if dist_on else None,
                                               post=not args.diag_forward_only)
-            return kc
+            return dets, keep, kc
         if pipeline:
             dets, keep, kc, _ = det.submit(timing=timing)
             if dist_on:  # the single collective, on the post stream after this batch's NMS
                 with torch.cuda.stream(det.s_post):
                     dets, kc, keep = gather_detections(dets, kc, keep)
-            return kc
+            return dets, keep, kc
         if timing is not None:
             timing[0].record()
         dets, keep, kc = det()
@@ -605,7 +622,7 @@ def timed_leg(args, det, mode, dist_on, gather, lat_ev, steps=None, latency_step
             dets, kc, keep = gather_detections(dets, kc, keep)
         if timing is not None:
             timing[1].record()
-        return kc
+        return dets, keep, kc
 
     def drain():
         if pipeline:
@@ -620,11 +637,13 @@ def timed_leg(args, det, mode, dist_on, gather, lat_ev, steps=None, latency_step
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(steps):
-        kc = step(i)
+        dets, keep, kc = step(i)
     drain()
     if dist_on:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    # the last timed step's outputs, before a later step reuses their slot
+    last = tuple(t.cpu() for t in (dets, keep, kc)) if getattr(args, 'dump_outputs', None) else None
     det.check()  # outside the timed region: no batch left the plan's range (fp16: |a| <= 65504)
     lat = [a.elapsed_time(b) for a, b in lat_ev]
     # unloaded latency: one batch in flight at a time (input resident -> detections, + gather)
@@ -637,7 +656,26 @@ def timed_leg(args, det, mode, dist_on, gather, lat_ev, steps=None, latency_step
         step()
         drain()
         lat1.append((time.perf_counter() - t1) * 1e3)
-    return elapsed, lat, lat1, kc
+    return elapsed, lat, lat1, kc, last
+
+
+def dump_outputs(path, dets, keep, kc):
+    """--dump-outputs: what the timed path returned in its last timed step, as
+    <path>/<name>.npy: dets float32 [n, max_det, 7] (rows past a batch's count are
+    zero), keep_rows [n, max_det] (-1 padded) and keep_counts [n] as float64 (exact
+    for int32). 270 KB at the default shape; a dump past 64 MB keeps a fixed, seeded
+    sample of the images instead (their indices in images.npy)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    n = dets.shape[0]
+    cap = int(64e6 // (dets[0].numel() * 4 + keep[0].numel() * 8 + 16))
+    if n > cap:
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, cap, replace=False)))
+        dets, keep, kc = dets[idx], keep[idx], kc[idx]
+        np.save(os.path.join(path, "images.npy"), idx.numpy().astype(np.float64))
+    np.save(os.path.join(path, "dets.npy"), dets.numpy().astype(np.float32, copy=False))
+    np.save(os.path.join(path, "keep_rows.npy"), keep.numpy().astype(np.float64))
+    np.save(os.path.join(path, "keep_counts.npy"), kc.numpy().astype(np.float64))
 
 
 def precision_leg(args, dev, rank, world, dist_on, gather, mode, precision, steps, sfx=None, with_roofline=True):
@@ -654,7 +692,8 @@ def precision_leg(args, dev, rank, world, dist_on, gather, mode, precision, step
     pipeline = False if mode == "serial" else mode
     _, det, _, _, _ = setup(a, dev, rank, pipeline=pipeline)
     lat_ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(steps)]
-    elapsed, lat, _, _ = timed_leg(a, det, mode, dist_on, gather, lat_ev, steps=steps, latency_steps=0)
+    a.dump_outputs = None
+    elapsed, lat, _, _, _ = timed_leg(a, det, mode, dist_on, gather, lat_ev, steps=steps, latency_steps=0)
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if dist_on:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -720,7 +759,11 @@ def main(argv=None):
         g_dets, g_kc, g_keep = gather_detections(dets, kc, keep)
         return g_dets, g_keep, g_kc
 
-    elapsed, lat, lat1, kc = timed_leg(args, det, mode, dist_on, gather, lat_ev)
+    full = args.full
+    elapsed, lat, lat1, kc, last = timed_leg(args, det, mode, dist_on, gather, lat_ev,
+                                             latency_steps=None if full else 0)
+    if last is not None and rank == 0:
+        dump_outputs(args.dump_outputs, *last)
     t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
     if dist_on:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -729,8 +772,10 @@ def main(argv=None):
     value = images / elapsed
     det1 = det.slots[0] if pipeline else det
 
-    img_in = image_in_leg(args, det, dev, dist_on, gather) if args.image_in_steps > 0 else None
-    rl = roofline(det1, args.roofline_steps, args.precision) if rank == 0 else None
+    # everything from here to the result line but the two figures read off the headline plan
+    # (flops_per_image, detections_last_step) takes GPU or CPU runs of its own: --full only
+    img_in = image_in_leg(args, det, dev, dist_on, gather) if full and args.image_in_steps > 0 else None
+    rl = roofline(det1, args.roofline_steps, args.precision) if full and rank == 0 else None
     flops_per_image = det1.engine.flops_per_image
     detections_last_step = int(kc.sum().item())
     # the fp16 (north_star 1e-3) leg: at most 30 timed steps by default, so a long headline run
@@ -738,6 +783,8 @@ def main(argv=None):
     n16 = args.fp16_steps if args.fp16_steps is not None else (min(args.steps, 30) if args.precision == "bf16" else 0)
     npl = args.pipelined_steps if args.pipelined_steps is not None else (min(args.steps, 30) if mode == "concurrent"
                                                                           else 0)
+    if not full:
+        n16 = npl = 0
     fp16 = pipelined = None
     legs = not args.diag_forward_only and ((n16 > 0 and args.precision != "fp16") or (npl > 0 and mode == "concurrent"))
     if legs:
@@ -749,7 +796,7 @@ def main(argv=None):
         pipelined = precision_leg(args, dev, rank, world, dist_on, gather, "pipelined", args.precision, npl,
                                   sfx="_pipelined", with_roofline=False)
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0:
+    if full and rank == 0 and world == 1 and args.cpu_seconds > 0:
         cpu = cpu_baseline(args, sd, cfg)
     if rank == 0:
         peak = PEAK[args.precision]
@@ -772,7 +819,8 @@ def main(argv=None):
                        "conf_thres": args.conf, "iou_thres": args.iou, "max_det": args.max_det},
             "mfma_fraction_whole_step": round(flops_per_image * value /
                                               (world * peak * 1e12), 4),
-            "roofline": {"bound": "mfma", "kernel": rl['kernel'], "achieved": round(rl['achieved'], 2), "peak": peak,
+            "roofline": None if rl is None else {  # --full
+                         "bound": "mfma", "kernel": rl['kernel'], "achieved": round(rl['achieved'], 2), "peak": peak,
                          "unit": "TFLOP/s", "frac": round(rl['achieved'] / peak, 4),
                          "traffic": pmc_traffic(rl['kernel'], shape, rnd),
                          "traffic_unit": "bytes/launch (HBM, PMC)", "traffic_round": rnd,
@@ -796,7 +844,7 @@ def main(argv=None):
             "detections_last_step": detections_last_step,
         }
         print(json.dumps(out), flush=True)
-        if os.environ.get("YCX_BENCH_KERNELS"):  # the per-op roofline gap table (serial leg, HIP events)
+        if rl is not None and os.environ.get("YCX_BENCH_KERNELS"):  # --full: the per-op roofline gap table
             with open(os.environ["YCX_BENCH_KERNELS"], "w") as f:
                 json.dump(dict(precision=args.precision, shape=list(shape), peak_tflops=peak,
                                hbm_peak_gbs=HBM_PEAK_GBS, forward_kernel_ms=rl['forward_kernel_ms'],

@@ -1,3 +1,4 @@
+import glob
 import json
 import os
 import sys
@@ -23,14 +24,25 @@ def manifest():
         return json.load(f)
 
 
+def _golden_parts(stem):
+    """The arrays of <stem>.<i>.npz, i = 0, 1, ...: make_golden.py writes the larger
+    fixtures in parts so that no committed file exceeds 1 MiB."""
+    parts = sorted(glob.glob(os.path.join(GOLD, stem + ".[0-9]*.npz")))
+    assert parts, f"no {stem}.<i>.npz under {GOLD}"
+    out = {}
+    for p in parts:
+        out.update(np.load(p))
+    return out
+
+
 @pytest.fixture(scope="session")
 def g1():
-    return dict(np.load(os.path.join(GOLD, "g1_ops.npz")))
+    return _golden_parts("g1_ops")
 
 
 @pytest.fixture(scope="session")
 def g2():
-    return dict(np.load(os.path.join(GOLD, "g2_nets.npz")))
+    return _golden_parts("g2_nets")
 
 
 @pytest.fixture(scope="session")

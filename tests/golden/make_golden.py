@@ -12,8 +12,8 @@ stored so tests can prove they regenerate the same tensors.
 
 Outputs (data only, no reference source):
   tests/golden/manifest.json             configs, seeds, shapes, hashes
-  tests/golden/g1_ops.npz                per-op mini networks (G1)
-  tests/golden/g2_nets.npz               yolov7 @160 bs1 nc80, yolov7-tiny @640 bs1 nc1 (G2)
+  tests/golden/g1_ops.<i>.npz            per-op mini networks (G1), in parts under 1 MiB
+  tests/golden/g2_nets.<i>.npz           yolov7 @160 bs1 nc80, yolov7-tiny @640 bs1 nc1 (G2), in parts
   tests/golden/g3_post.npz               decode + NMS (G3)
   yolo-continuous_amd/ycx/cfg/net/*.json the reference network YAMLs as JSON
 """
@@ -55,6 +55,34 @@ def arr_hash(arrs):
     for a in arrs:
         h.update(np.ascontiguousarray(a).tobytes())
     return h.hexdigest()
+
+
+PART_BYTES = 900_000  # every committed fixture file stays under 1 MiB
+
+
+def save_parts(stem, arrays):
+    """Write ``arrays`` as <stem>.0.npz, <stem>.1.npz, ... in key order, each at most
+    PART_BYTES of array data (tests/conftest.py reads the parts back into one dict)."""
+    import glob
+    for p in glob.glob(os.path.join(GOLD, stem + '.[0-9]*.npz')):
+        os.remove(p)
+    parts, size = [{}], 0
+    for k, a in arrays.items():
+        if parts[-1] and size + a.nbytes > PART_BYTES:
+            parts.append({})
+            size = 0
+        parts[-1][k] = a
+        size += a.nbytes
+    for i, part in enumerate(parts):
+        np.savez(os.path.join(GOLD, f'{stem}.{i}.npz'), **part)
+
+
+def load_parts(stem):
+    import glob
+    out = {}
+    for p in sorted(glob.glob(os.path.join(GOLD, stem + '.[0-9]*.npz'))):
+        out.update(np.load(p))
+    return out
 
 
 def import_reference():
@@ -160,11 +188,11 @@ def make_idetect_eval(Model, manifest):
 
 
 def add_g1(Model, names):
-    """Append G1 cases (by name) to an existing g1_ops.npz / manifest; the seeds
+    """Append G1 cases (by name) to the existing g1_ops parts / manifest; the seeds
     come from the case's position in mini_nets(), exactly as a full run sets them."""
     with open(os.path.join(GOLD, 'manifest.json')) as f:
         manifest = json.load(f)
-    g1 = dict(np.load(os.path.join(GOLD, 'g1_ops.npz')))
+    g1 = load_parts('g1_ops')
     nets = list(mini_nets().items())
     for i, (name, (cfg, nc)) in enumerate(nets):
         if name not in names:
@@ -181,7 +209,7 @@ def add_g1(Model, names):
         if strides is not None:
             manifest['g1'][name]['strides'] = strides
         print('G1+', name, [o.shape for o in outs])
-    np.savez(os.path.join(GOLD, 'g1_ops.npz'), **g1)
+    save_parts('g1_ops', g1)
     with open(os.path.join(GOLD, 'manifest.json'), 'w') as f:
         json.dump(manifest, f, indent=1)
 
@@ -219,7 +247,7 @@ def main():
         if strides is not None:
             manifest['g1'][name]['strides'] = strides
         print('G1', name, [o.shape for o in outs])
-    np.savez(os.path.join(GOLD, 'g1_ops.npz'), **g1)
+    save_parts('g1_ops', g1)
 
     # ---- G2: full networks ----
     g2 = {}
@@ -232,7 +260,7 @@ def main():
         manifest['g2'][name] = dict(net=net, nc=nc, shape=[1, 3, hw, hw], img_seed=7, w_seed=0, sd_hash=h,
                                     n_keys=nkeys, out_shapes=[list(o.shape) for o in outs])
         print('G2', name, nkeys, [o.shape for o in outs])
-    np.savez(os.path.join(GOLD, 'g2_nets.npz'), **g2)
+    save_parts('g2_nets', g2)
 
     # ---- G3: decode + NMS from synthetic head logits ----
     g3 = {}

@@ -170,3 +170,23 @@ def test_visible_gpus_from_kfd_topology(tmp_path):
     assert bench.visible_gpus(env={}, kfd_nodes=str(tmp_path)) == 2
     assert bench.visible_gpus(env={}, kfd_nodes=str(tmp_path / "missing")) is None
     assert bench.visible_gpus(env={"ROCR_VISIBLE_DEVICES": "0,1,2", "HIP_VISIBLE_DEVICES": "1"}) == 1
+
+
+def test_bench_dump_outputs_files(tmp_path):
+    """--dump-outputs / --full parse (both off by default), and dump_outputs writes the
+    step's three arrays as float32 / float64 .npy with their values intact."""
+    import bench
+    a = bench.parse([])
+    assert a.full is False and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", str(tmp_path / "d")])
+    assert a.full is True and a.dump_outputs == str(tmp_path / "d")
+    g = torch.Generator().manual_seed(3)
+    dets = torch.rand((4, 5, 7), generator=g)
+    keep = torch.randint(-1, 2 ** 31 - 1, (4, 5), dtype=torch.int32, generator=g)
+    kc = torch.tensor([0, 5, 70000, 2 ** 31 - 1], dtype=torch.int32)
+    bench.dump_outputs(a.dump_outputs, dets, keep, kc)
+    got = {n: np.load(tmp_path / "d" / f"{n}.npy") for n in ("dets", "keep_rows", "keep_counts")}
+    assert sorted(p.name for p in (tmp_path / "d").iterdir()) == ["dets.npy", "keep_counts.npy", "keep_rows.npy"]
+    assert got["dets"].dtype == np.float32 and np.array_equal(got["dets"], dets.numpy())
+    assert got["keep_rows"].dtype == np.float64 and np.array_equal(got["keep_rows"], keep.numpy())
+    assert got["keep_counts"].dtype == np.float64 and np.array_equal(got["keep_counts"], kc.numpy())

@@ -1,6 +1,6 @@
 """Render bench.py's per-op roofline gap table (YCX_BENCH_KERNELS=<file>) as markdown.
 
-    YCX_BENCH_KERNELS=gpurun_out/ops.json python bench.py ...
+    YCX_BENCH_KERNELS=ops.json python bench.py --full ...
     python tools/op_gap.py gpurun_out/ops.json > profiles/r04/op_gap.md
 
 Each row: the op's measured time (HIP events around every op of a serial forward), its

@@ -13,7 +13,7 @@ export TMPDIR=/tmp
 run() {  # name, bench args...
   local name=$1; shift
   YCX_BENCH_KERNELS=$OUT/side_${name}_ops.json timeout -k 10 400 rocprofv3 --kernel-trace --stats \
-    -d "$OUT/side_$name" -o run --output-format csv -- python3 "$ROOT/bench.py" --cpu-seconds 0 --steps 40 "$@" \
+    -d "$OUT/side_$name" -o run --output-format csv -- python3 "$ROOT/bench.py" --full --cpu-seconds 0 --steps 40 "$@" \
     > "$OUT/side_$name.log" 2>&1
   grep '^{"metric' "$OUT/side_$name.log" | tail -n 1 > "$OUT/side_$name.json"
   cut -c1-160 "$OUT/side_$name.json"

@@ -1,6 +1,6 @@
 """Per-kernel duration statistics of one leg of a rocprofv3 kernel trace (development tool).
 
-bench.py runs three legs on the GPU: the warm-up + timed loop (three batches in
+bench.py --full runs three legs on the GPU: the warm-up + timed loop (three batches in
 flight on three streams, so kernels of different batches overlap and each
 kernel's wall duration includes the time it shares the GPU), then the roofline
 leg (``--roofline-steps`` serial eager forwards of one plan on one stream, the
