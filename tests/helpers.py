@@ -241,3 +241,68 @@ def decoded_flip_report(dec_dev, dec_ref, nc, conf, iou):
     return dict(n_pass_dev=len(pd_), n_pass_ref=len(pr), member_flips=len(member), member_far=member_far,
                 max_score_delta=delta, cls_flips=cls_flips, n_keep_dev=len(kd), n_keep_ref=len(kr),
                 keep_flips=len(flipped), flip_classes=classes, unexplained_flips=unexplained)
+
+
+# ---- exact-operand parity (tests/test_gpu_conv_exact.py) ----
+# Operands and bias that are small dyadic rationals make every product and every partial sum of a
+# convolution exactly representable in fp32, so the fp32 accumulator holds the true sum whatever the
+# order of the additions, and the stored element must be RNE(true sum) bit for bit.
+_ELT_INT = {torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.float32: torch.int32}
+
+
+def dyadic(shape, lo, hi, step, gen):
+    """float64 tensor of uniformly drawn multiples of ``step`` in [lo, hi] (lo, hi multiples of step)."""
+    k_lo, k_hi = round(lo / step), round(hi / step)
+    assert k_lo * step == lo and k_hi * step == hi
+    return torch.randint(k_lo, k_hi + 1, tuple(shape), generator=gen).double() * step
+
+
+def rne(t64, dtype):
+    """The reference element: torch's CPU cast of the float64 value (round to nearest, ties to even).
+    The cast goes through fp32; that is one rounding for every value fp32 holds exactly (all the
+    exact-operand sums), and otherwise moves the result only for a value within 2^-24 relative of
+    a rounding boundary."""
+    return t64.to(torch.float64).to(dtype)
+
+
+def _elt_key(t):
+    """Sign-magnitude bit pattern -> an integer that counts representable values in order."""
+    it = _ELT_INT[t.dtype]
+    bits = t.contiguous().view(it).to(torch.int64)
+    mag = bits & (0x7FFF if it == torch.int16 else 0x7FFFFFFF)
+    return torch.where(bits < 0, -mag, mag)
+
+
+def _elt_from_key(key, dtype):
+    it = _ELT_INT[dtype]
+    top = 0x8000 if it == torch.int16 else 0x80000000
+    bits = torch.where(key < 0, (-key) | top, key)
+    bits = torch.where(bits >= top, bits - 2 * top, bits)  # two's complement of the sign bit
+    return bits.to(it).view(dtype)
+
+
+def elt_ulps(got, ref, dtype):
+    """Signed distance got - ref in representable values of ``dtype`` (+0 and -0 coincide)."""
+    assert got.dtype == dtype and ref.dtype == dtype
+    return _elt_key(got) - _elt_key(ref)
+
+
+def elt_neighbours(t64, dtype):
+    """(below, above) as float64: the representable values of ``dtype`` that bracket t64
+    (both equal to t64 where it is representable)."""
+    r = rne(t64, dtype)
+    k, r64 = _elt_key(r), r.double()
+    up = _elt_from_key(k + 1, dtype).double()
+    dn = _elt_from_key(k - 1, dtype).double()
+    lo = torch.where(r64 <= t64, r64, dn)
+    hi = torch.where(r64 >= t64, r64, up)
+    return lo, hi
+
+
+def rounding_stats(t64, dtype):
+    """(share of elements not representable in ``dtype``, share that are exact ties between two
+    adjacent representable values): what a store has to get right on these values."""
+    lo, hi = elt_neighbours(t64, dtype)
+    inexact = lo != hi
+    tie = inexact & ((t64 - lo) == (hi - t64))
+    return float(inexact.double().mean()), float(tie.double().mean())

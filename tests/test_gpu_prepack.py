@@ -30,6 +30,37 @@ def test_prepack_roundtrip_bit_exact(device, tmp_path, precision):
         assert torch.equal(a, b)
 
 
+@pytest.mark.parametrize('precision', ['bf16', 'fp16'])
+def test_prepack_silu_pack_mismatch_raises(device, tmp_path, monkeypatch, precision):
+    """A file saved with the SiLU convs packed plain (YCX_NO_SILU_PS) records silu_ps = False;
+    loading it where they run pre-scaled raises (and the reverse) instead of running the wrong
+    epilogue on the weights; the matched round trip is bit-exact under that setting too."""
+    from ycx import engine
+    x = synthetic_images(2, 3, 160, 160, seed=4).to(device)
+    monkeypatch.setattr(engine, '_NO_SILU_PS', True)
+    src, _ = make_model('yolov7-tiny', 1, 0, precision)
+    src.to(device)
+    ref = [o.clone() for o in src(x)]
+    plain = str(tmp_path / "plain.safetensors")
+    assert src.save_prepacked(plain, (160, 160))['silu_ps'] is False
+    dst, _ = make_model('yolov7-tiny', 1, 7, 'bf16')
+    dst.load_prepacked(plain)
+    dst.to(device)
+    for a, b in zip(dst(x), ref):
+        assert torch.equal(a, b)
+    monkeypatch.setattr(engine, '_NO_SILU_PS', False)
+    other, _ = make_model('yolov7-tiny', 1, 7, 'bf16')
+    with pytest.raises(ValueError, match='silu_ps'):
+        other.load_prepacked(plain)
+    src2, _ = make_model('yolov7-tiny', 1, 0, precision)
+    src2.to(device)
+    scaled = str(tmp_path / "scaled.safetensors")
+    assert src2.save_prepacked(scaled, (160, 160))['silu_ps'] is True
+    monkeypatch.setattr(engine, '_NO_SILU_PS', True)
+    with pytest.raises(ValueError, match='silu_ps'):
+        other.load_prepacked(scaled)
+
+
 def test_prepack_rejects_other_plan(device, tmp_path):
     src, _ = make_model('yolov7-tiny', 1, 0, 'bf16')
     src.to(device)

@@ -56,3 +56,65 @@ def test_decoded_flip_report_attribution():
     r = decoded_flip_report(e, d, 1, 0.3, 0.3)
     assert r['keep_flips'] == 3 and r['member_flips'] == 1 and r['member_far'] == 0, r
     assert r['unexplained_flips'] == 0 and r['flip_classes'] == 1, r
+
+
+@pytest.mark.parametrize('dtype_name', ['bfloat16', 'float16'])
+def test_exact_comparator_bites(dtype_name):
+    """The comparator of tests/test_gpu_conv_exact.py (bit patterns against helpers.rne of the float64
+    sum, distances by helpers.elt_ulps) on a cin 64, 3x3 reference: it must report each of
+    (a) truncation toward zero in place of RNE, (b) round-half-away in place of ties-to-even, (c) one
+    dropped term of magnitude 1/16, (d) slope 0.1 where the descriptor says 0.125 -- and nothing on
+    the correctly rounded result."""
+    import torch
+    import torch.nn.functional as F
+    from helpers import dyadic, elt_neighbours, elt_ulps, rne, rounding_stats
+    tdt = getattr(torch, dtype_name)
+    sx, sw = (1 / 4, 1 / 4) if tdt == torch.bfloat16 else (1 / 16, 1 / 8)  # the GPU cases' grids at K = 576
+    g = torch.Generator().manual_seed(0)
+    x = dyadic((1, 64, 9, 10), -4, 4, sx, g)
+    w = dyadic((32, 64, 3, 3), -2, 2, sw, g)
+    b = dyadic((32,), -2, 2, 1 / 16, g)
+    z = F.conv2d(x, w, b, 1, 1)
+    assert torch.equal(F.conv2d(x.float(), w.float(), b.float(), 1, 1).double(), z)  # fp32 holds every sum
+    rounded, ties = rounding_stats(z, tdt)
+    assert rounded >= 0.10 and ties >= 0.01
+    ref = rne(z, tdt)
+
+    def mismatches(got):
+        return int((got.view(torch.int16) != ref.view(torch.int16)).sum())
+
+    assert mismatches(z.to(tdt)) == 0 and not elt_ulps(z.to(tdt), ref, tdt).any()
+    lo, hi = elt_neighbours(z, tdt)
+    assert bool((lo <= z).all() and (z <= hi).all() and ((lo == hi) == (ref.double() == z)).all())
+    # (a) truncation toward zero: wrong wherever RNE rounds away from zero
+    trunc = torch.where(z >= 0, lo, hi).to(tdt)
+    n_a = mismatches(trunc)
+    assert n_a >= 0.05 * z.numel() and int(elt_ulps(trunc, ref, tdt).abs().max()) == 1
+    # (b) round-half-away: wrong on the ties whose even neighbour is the one nearer zero
+    tie = (lo != hi) & ((z - lo) == (hi - z))
+    away = torch.where(tie, torch.where(z >= 0, hi, lo), ref.double()).to(tdt)
+    n_b = mismatches(away)
+    assert 0 < n_b <= int(tie.sum()) and n_b >= 0.25 * int(tie.sum())
+    assert bool((elt_ulps(away, ref, tdt) != 0)[~tie].sum() == 0)
+    # (c) one term of magnitude 1/16 dropped from one output whose neighbours are at most 1/16 apart
+    #     (|z| < 16 in bf16; any output in fp16, whose sums stay far below 2^7): that element is reported
+    idx = next(i for i in (z.abs() < 16).nonzero().tolist())
+    dropped = z.clone()
+    dropped[tuple(idx)] -= 1 / 16
+    got_c = dropped.to(tdt)
+    assert mismatches(got_c) == 1 and elt_ulps(got_c, ref, tdt)[tuple(idx)] != 0
+    #     and the same term (one tap of one input channel, |x w| = 1/16) dropped by every output pixel
+    xs, ws = x.clone(), w.clone()
+    xs[:, 5], ws[:, 5, 1, 1] = 1 / 4, 1 / 4
+    z_all = F.conv2d(xs, ws, b, 1, 1)
+    ws[:, 5, 1, 1] = 0
+    z_drop = F.conv2d(xs, ws, b, 1, 1)
+    assert torch.equal(z_all - z_drop, torch.full_like(z_all, 1 / 16))
+    assert int((z_drop.to(tdt).view(torch.int16) != rne(z_all, tdt).view(torch.int16)).sum()) >= 0.3 * z.numel()
+    # (d) leaky slope 0.1 (computed in fp32, as an epilogue would) where the reference uses 0.125
+    ref_d = rne(torch.where(z > 0, z, z * 0.125), tdt)
+    zf = z.float()
+    got_d = torch.where(zf > 0, zf, zf * 0.1).to(tdt)
+    neg = z < 0
+    bad_d = got_d.view(torch.int16) != ref_d.view(torch.int16)
+    assert int(bad_d[neg].sum()) >= 0.9 * int(neg.sum()) and not bad_d[~neg].any()

@@ -154,6 +154,47 @@ def test_prepack_file_format_checks(tmp_path):
     assert h == prepack.state_dict_sha256(m) and len(h) == 64
 
 
+def test_prepack_refuses_old_format_and_silu_pack_mismatch(tmp_path, monkeypatch):
+    """A format-4 file does not say whether its SiLU convs were packed x -log2(e): refused.
+    A format-5 file records it (silu_ps), and Model.load_prepacked refuses a file whose
+    record differs from the running YCX_NO_SILU_PS setting (the wrong epilogue would run on
+    the weights with no other sign); an fp32 plan is never pre-scaled, so it loads either way."""
+    import json
+    from safetensors.torch import save_file
+    from ycx import engine, prepack
+    assert prepack.FORMAT == "ycx-prepack-5"
+    p = str(tmp_path / "f.safetensors")
+
+    def write(**kw):
+        meta = dict(format=prepack.FORMAT, precision='bf16', hw=[64, 64], n_tensors=1, fp8_amax=None,
+                    state_dict_sha256='0' * 64, silu_ps=True)
+        meta.update(kw)
+        save_file({"p0": torch.zeros(2)}, p, metadata={"ycx": json.dumps(meta)})
+
+    m, _ = make_model('yolov7-tiny', 1, 0)
+    write(format="ycx-prepack-4")
+    with pytest.raises(ValueError, match="ycx-prepack-4"):
+        m.load_prepacked(p)
+    for no_ps in (False, True):
+        monkeypatch.setattr(engine, '_NO_SILU_PS', no_ps)
+        assert prepack.silu_ps_setting('bf16') == (not no_ps) and prepack.silu_ps_setting('f32') is False
+        for precision in ('bf16', 'fp16'):
+            write(precision=precision, silu_ps=no_ps)  # packed under the other setting
+            with pytest.raises(ValueError, match="silu_ps"):
+                m.load_prepacked(p)
+            assert not m._prepacked  # nothing was bound
+            write(precision=precision, silu_ps=not no_ps)
+            assert m.load_prepacked(p)['silu_ps'] == (not no_ps)
+            m._prepacked.clear()
+        write(precision='f32', silu_ps=False)
+        m.load_prepacked(p)
+        m._prepacked.clear()
+    write(silu_ps=None)  # a null record counts as "not pre-scaled"
+    monkeypatch.setattr(engine, '_NO_SILU_PS', False)
+    with pytest.raises(ValueError, match="silu_ps"):
+        m.load_prepacked(p)
+
+
 def test_unfused_upsample_writes_its_concat_slice(manifest):
     """An upsample that cannot fuse (its producer is a pool) and lands in the
     middle of a concat buffer keeps that channel offset (the copy

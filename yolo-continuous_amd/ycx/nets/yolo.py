@@ -324,11 +324,16 @@ class Model(nn.Module):
         """Use the packed weights of a ycx.prepack file for its (precision, H, W)
         plan instead of folding this module's parameters, and switch to its
         precision. strict: the file must come from this module's current
-        state_dict."""
+        state_dict. A file whose SiLU convs were packed under the other
+        YCX_NO_SILU_PS setting than this process runs is refused (ValueError)."""
         from .. import prepack
         meta, tensors = prepack.load(path)
         if strict and meta.get('state_dict_sha256') != prepack.state_dict_sha256(self):
             raise ValueError(f"ycx: {path} was packed from a different state_dict")
+        if bool(meta.get('silu_ps')) != prepack.silu_ps_setting(meta['precision']):
+            # the epilogue would not match the weights: SiLU of pre-scaled sums, or the reverse
+            raise ValueError(f"ycx: {path} was packed with silu_ps={meta.get('silu_ps')!r}, this process runs "
+                             f"silu_ps={prepack.silu_ps_setting(meta['precision'])!r} (YCX_NO_SILU_PS)")
         hw = tuple(meta['hw'])
         self.set_precision(meta['precision'])
         self._prepacked[(meta['precision'],) + hw] = tensors

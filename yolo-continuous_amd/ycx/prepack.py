@@ -12,7 +12,7 @@ The file holds one plan (precision, input H x W): tensors ``p<2i>, p<2i+1>`` =
 the packed weights and bias of the i-th conv / stem node of the lowered graph
 (named by node, not by packing order, so the fusions that vary with the batch
 size -- the 1x1 pair -- cannot permute them) and ``metadata['ycx']`` = JSON {format, precision, hw,
-n_tensors, fp8_amax, state_dict_sha256}. The batch size is free: packed weights
+n_tensors, fp8_amax, state_dict_sha256, silu_ps}. The batch size is free: packed weights
 do not depend on it. Loading checks every tensor's shape and dtype against the
 plan it is bound to, and refuses a file written for another plan.
 
@@ -29,8 +29,16 @@ import json
 
 import torch
 
-FORMAT = "ycx-prepack-4"  # 3 (r05): tensors named by conv node (2i, 2i+1), independent of which convs fuse;
+FORMAT = "ycx-prepack-5"  # 3 (r05): tensors named by conv node (2i, 2i+1), independent of which convs fuse;
 #                            4 (r06): SiLU convs of 16-bit / fp8 plans packed pre-scaled by -log2(e) (YCX_ACT_SILU_PS)
+#                            5: metadata records whether they were (silu_ps); a load under the other setting is refused
+
+
+def silu_ps_setting(precision):
+    """Whether the running process packs (and runs) the SiLU convs of a ``precision`` plan
+    pre-scaled by -log2(e): every 16-bit / fp8 plan unless YCX_NO_SILU_PS is set; never fp32."""
+    from . import engine
+    return precision != "f32" and not engine._NO_SILU_PS
 
 
 def state_dict_sha256(model):
@@ -52,7 +60,7 @@ def save(model, path, hw, precision=None, device="cuda"):
         tensors = {k: t.detach().cpu().contiguous() for k, t in eng.packed.items()}
         meta = dict(format=FORMAT, precision=precision, hw=[int(hw[0]), int(hw[1])], n_tensors=len(tensors),
                     fp8_amax=model._fp8_amax.get((int(hw[0]), int(hw[1]))) if precision == "fp8" else None,
-                    state_dict_sha256=state_dict_sha256(model))
+                    state_dict_sha256=state_dict_sha256(model), silu_ps=silu_ps_setting(precision))
     finally:
         model.set_precision(old)
     save_file(tensors, path, metadata={"ycx": json.dumps(meta)})
