@@ -240,6 +240,11 @@ typedef struct ycx_op {
   int32_t* status;          /* HEAD (nullable): the range guard flag, below         */
   void* out2;               /* CONV_PAIR: the second conv's output (out: the first's, nullable) */
   void* workspace;          /* CONV with d.conv.k_split > 1: fp32 partials, >= ycx_conv_workspace_size */
+  /* CONV_PAIR with out3 set: ycx_conv2d_pair_pool, the pair plus the pooled 1x1 `conv3` */
+  ycx_conv_desc conv3;
+  const void* weight3;      /* conv3's packed weights                               */
+  const float* bias3;       /* conv3's bias                                         */
+  void* out3;               /* conv3's output; null: a plain pair                   */
 } ycx_op;
 
 int ycx_abi_version(void);
@@ -294,6 +299,19 @@ ycx_status ycx_conv2d_head(const ycx_conv_desc* d, const ycx_head_desc* h, const
 ycx_status ycx_conv2d_pair(const ycx_conv_desc* a, const ycx_conv_desc* b, const void* x, const void* w_a,
                            const float* bias_a, void* ya, const void* w_b, const float* bias_b, void* yb,
                            void* stream);
+/* ycx_conv2d_pair plus the 1x1 conv of the MP branch that also reads `a`'s output:
+ * yc = act_c(W_c MP(ya) + b_c) (256 -> cout_pad 128, cout % 8 == 0), MP the k2 s2 max-pool
+ * (nets/common.py:25-31), pooled from the ya tile on chip: yolov7 layers 11 -> 14 and
+ * 11 -> 12 -> 13. With `ya` null the 256-channel map is neither written nor read back.
+ * `c` is the descriptor ycx_conv2d would take for the pooled conv (c->in_pool == 1,
+ * c->h == a->h / 2, c->w == a->w / 2, c->cin == 256; its in_c_* are not used). The launch
+ * walks tiles of two image rows x 32 columns: a->h % 2 == 0 and a->w % 32 == 0.
+ * YCX_ERR_UNSUPPORTED otherwise. ya / yb as ycx_conv2d_pair; yc bit-identical to
+ * ycx_conv2d(c) on the stored ya. */
+ycx_status ycx_conv2d_pair_pool(const ycx_conv_desc* a, const ycx_conv_desc* b, const ycx_conv_desc* c,
+                                const void* x, const void* w_a, const float* bias_a, void* ya, const void* w_b,
+                                const float* bias_b, void* yb, const void* w_c, const float* bias_c, void* yc,
+                                void* stream);
 /* Stem conv: fp32 NCHW input (the model input, cin <= 4), weights fp32
  * [kh][kw][cin][cout_pad], output NHWC in d->dtype. in_c_* describe the NCHW
  * channel count (in_c_stride = channels of the input tensor). */

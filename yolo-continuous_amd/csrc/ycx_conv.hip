@@ -2794,9 +2794,11 @@ __global__ void __launch_bounds__(WCO * WPX * 64) conv1x1_wres(ConvArgs a) {
 // bs 32: 419 MB less read). Both epilogues apply the same float operations as
 // conv1x1_wres's, so y1 and y2 are bit-identical to the two unfused launches.
 // The ring's counted vmcnt waits include both conversions' stores.
+// TRIO (conv1x1_wres_pair_pool, below): the same body over two-row x 32-column tiles, with the
+// tile's 2x2 max-pool formed in LDS after epilogue 1 and a third conv (256 -> 128) on it.
 // -------------------------------------------------------------------------
-template <int KC, int NS, int SUB, int CO2>
-__global__ void __launch_bounds__(512) conv1x1_wres_pair(ConvArgs a, ConvArgs b) {
+template <int KC, int NS, int SUB, int CO2, bool TRIO>
+__device__ __forceinline__ void wres_pair_body(const ConvArgs& a, const ConvArgs& b, const ConvArgs& c3) {
   constexpr int NW = 8, PT = 64, FM = 2, FN = 4, KS = KC / SUB, SLAB = PT * 128, STAGE = SUB * SLAB;
   constexpr int A_PW = PT / (8 * NW);
   constexpr int K2 = 256, FN2 = CO2 == 128 ? 2 : 4;  // second conv: K = 256, pixels per wave 16 FN2
@@ -2804,8 +2806,14 @@ __global__ void __launch_bounds__(512) conv1x1_wres_pair(ConvArgs a, ConvArgs b)
   static_assert(KC % SUB == 0 && A_PW == 1, "slabs per stage");
   constexpr int VM_RING = A_PW * SUB * (NS - 2);
   constexpr int Y1_BYTES = (K2 / 64) * SLAB;  // y1 tile: 4 slabs of 64 pixels x 128 B
-  __shared__ __attribute__((aligned(1024))) char smem[NS * STAGE + Y1_BYTES];
+  constexpr int P1_SLAB = 16 * 128, P1_BYTES = TRIO ? (K2 / 64) * P1_SLAB : 0;  // pooled tile: 4 slabs of 16 pixels
+  constexpr int K3R = 4;  // third conv: K chunks of W3 held in VGPRs; the other K2 / 32 - K3R in LDS
+  constexpr int W3_BYTES = TRIO ? NW * (K2 / 32 - K3R) * 1024 : 0, BS_BYTES = TRIO ? (256 + 256 + 128) * 4 : 0;
+  __shared__ __attribute__((aligned(1024))) char smem[NS * STAGE + Y1_BYTES + P1_BYTES + W3_BYTES + BS_BYTES];
   char* const y1s = smem + NS * STAGE;
+  char* const p1s = y1s + Y1_BYTES;
+  char* const w3s = p1s + P1_BYTES;
+  char* const bss = w3s + W3_BYTES;
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   const int L = ycx_xcd_remap(blockIdx.x, a.nwg);
   const int R = a.nwg;
@@ -2813,6 +2821,17 @@ __global__ void __launch_bounds__(512) conv1x1_wres_pair(ConvArgs a, ConvArgs b)
   const int t0 = (int)((long long)L * T / R), t1 = (int)((long long)(L + 1) * T / R);
   if (t0 >= t1) return;  // whole block: no barrier is left waiting
   const int m16 = lane & 15;
+  // TRIO: tile t is image rows 2q, 2q+1 (q = t / wb counts row pairs across the batch: h is even) x
+  // columns 32 cb .. +31 (cb = t % wb, wb = w / 32); tile row r is pixel tile_px(t) + row_px(r).
+  // Every tile is whole (M = 64 T) and holds the 16 complete 2x2 windows of pooled row q,
+  // columns 16 cb .. +15.
+  const int wb = TRIO ? a.W >> 5 : 1;
+  auto tile_px = [&](int t) {
+    if constexpr (!TRIO) return t * PT;
+    const int q = t / wb;
+    return 2 * q * a.W + 32 * (t - q * wb);
+  };
+  auto row_px = [&](int r) { return TRIO ? (r >> 5) * a.W + (r & 31) : r; };
 
   // first conv: this wave's 32 output channels (rows permuted as conv1x1_wres)
   const int cob = wid * 32;
@@ -2826,7 +2845,8 @@ __global__ void __launch_bounds__(512) conv1x1_wres_pair(ConvArgs a, ConvArgs b)
                                                    32 * kq + 8 * (lane >> 4));
   f32x4 bv[FM];
 #pragma unroll
-  for (int i = 0; i < FM; ++i) bv[i] = *reinterpret_cast<const f32x4*>(a.bias + cob + 8 * (lane >> 4) + 4 * i);
+  for (int i = 0; i < FM; ++i)
+    if constexpr (!TRIO) bv[i] = *reinterpret_cast<const f32x4*>(a.bias + cob + 8 * (lane >> 4) + 4 * i);
   // second conv: channels cob2 .. +31, pixels 16 FN2 h2 .. of every tile
   const int cob2 = CO2 == 128 ? (wid & 3) * 32 : wid * 32, h2 = CO2 == 128 ? wid >> 2 : 0;
   const elt_t* __restrict__ W2 = reinterpret_cast<const elt_t*>(b.w);
@@ -2841,23 +2861,47 @@ __global__ void __launch_bounds__(512) conv1x1_wres_pair(ConvArgs a, ConvArgs b)
 #pragma unroll
   for (int i = 0; i < FM; ++i) {
     const int co = cob2 + 8 * (lane >> 4) + 4 * i;
-    bv2[i] = co < b.Cout ? *reinterpret_cast<const f32x4*>(b.bias + co) : f32x4{0.f, 0.f, 0.f, 0.f};
+    if constexpr (!TRIO) bv2[i] = co < b.Cout ? *reinterpret_cast<const f32x4*>(b.bias + co) : f32x4{0.f, 0.f, 0.f, 0.f};
   }
+  // third conv (TRIO): channels cob3 .. +15 of the 16 pooled pixels, one fragment per wave
+  // (rows in channel order: C rows 4g .. 4g+3 are channels cob3 + 4g .., one 8-byte store per lane)
+  // The 256-VGPR budget of a two-wave SIMD holds W1, W2 and half of this wave's W3 rows (K chunks
+  // 0 .. K3R-1); the other half stays in LDS for the whole launch in fragment order (w3s: written and
+  // read by this wave only, 1 KiB per chunk), and so do the three bias vectors (bs).
+  const int cob3 = wid * 16;
+  eltx8 af3[TRIO ? K3R : 1];
+  if constexpr (TRIO) {
+    const elt_t* __restrict__ W3 = reinterpret_cast<const elt_t*>(c3.w);
+#pragma unroll
+    for (int kq = 0; kq < K2 / 32; ++kq) {
+      const eltx8 wv =
+          *reinterpret_cast<const eltx8*>(W3 + (size_t)(cob3 + m16) * c3.Ktot + 32 * kq + 8 * (lane >> 4));
+      if (kq < K3R) af3[kq] = wv;
+      else *reinterpret_cast<eltx8*>(w3s + (wid * (K2 / 32 - K3R) + kq - K3R) * 1024 + lane * 16) = wv;
+    }
+    float* bs = reinterpret_cast<float*>(bss);
+    if (tid < 256) bs[tid] = a.bias[tid];
+    else bs[tid] = tid - 256 < b.Cout ? b.bias[tid - 256] : 0.f;
+    if (tid < 128) bs[512 + tid] = tid < c3.Cout ? c3.bias[tid] : 0.f;
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // before the first ring barrier, which every epilogue follows
+  }
+  // the bias of channels co .. co+3 (TRIO: from bs; set: 0, 256, 512 for the three convs)
+  auto bias4 = [&](int set, int co) { return *reinterpret_cast<const f32x4*>(bss + (set + co) * 4); };
 
   // LDS-DMA of x: wave-instruction wid fills rows 8 wid .. +7 of a slab
   const elt_t* __restrict__ X = reinterpret_cast<const elt_t*>(a.x);
   const int x_bytes = a.M * a.in_cs * 2;
   const int lrow = lane >> 3, pch = lane & 7;
   const int rrow = 8 * wid + lrow;
-  const int roff = (rrow * a.in_cs + a.in_coff + ((pch ^ swz<64>(rrow)) << 3)) * 2;
+  const int roff = (row_px(rrow) * a.in_cs + a.in_coff + ((pch ^ swz<64>(rrow)) << 3)) * 2;
   const int nst = (t1 - t0) * KS;
   auto issue = [&](int s) {
     const int tl = s / KS, ks = s - tl * KS;
-    const int px0 = (t0 + tl) * PT;
+    const int px0 = tile_px(t0 + tl);
     char* base = smem + (s % NS) * STAGE;
 #pragma unroll
     for (int sb = 0; sb < SUB; ++sb) {
-      const int off = px0 + rrow < a.M ? px0 * a.in_cs * 2 + roff + (ks * SUB + sb) * 128 : 0x7FFFFFF0;
+      const int off = px0 + row_px(rrow) < a.M ? px0 * a.in_cs * 2 + roff + (ks * SUB + sb) * 128 : 0x7FFFFFF0;
       buf_lds16(X, x_bytes, off, 0, base + sb * SLAB + wid * 1024);
     }
   };
@@ -2865,11 +2909,13 @@ __global__ void __launch_bounds__(512) conv1x1_wres_pair(ConvArgs a, ConvArgs b)
 
   // every full tile stores exactly NSTO 16-byte vectors per wave (both outputs whole)
   const bool store1 = a.y != nullptr;
-  constexpr int NSTO_MAX = FN + FN2;
-  const int nsto = (store1 ? FN : 0) + FN2;
-  const bool exact = b.Cout == b.Cout_pad;  // a.Cout == a.Cout_pad == 256 (host check)
+  constexpr int NSTO_MAX = FN + FN2 + (TRIO ? 1 : 0);
+  const int nsto = (store1 ? FN : 0) + FN2 + (TRIO ? 1 : 0);
+  // a.Cout == a.Cout_pad == 256 (host check)
+  const bool exact = b.Cout == b.Cout_pad && (!TRIO || c3.Cout == c3.Cout_pad);
   elt_t* __restrict__ Y1 = store1 ? reinterpret_cast<elt_t*>(a.y) + a.out_coff : nullptr;
   elt_t* __restrict__ Y2 = reinterpret_cast<elt_t*>(b.y) + b.out_coff;
+  elt_t* __restrict__ Y3 = TRIO ? reinterpret_cast<elt_t*>(c3.y) + c3.out_coff : nullptr;
   int t = 0;
   for (int tl = 0; tl < t1 - t0; ++tl) {
     f32x4 acc[FM][FN];
@@ -2911,7 +2957,7 @@ __global__ void __launch_bounds__(512) conv1x1_wres_pair(ConvArgs a, ConvArgs b)
     }
     // epilogue 1: y1 to HBM (when stored) and, as the second conv's B operand, to LDS.
     // The previous tile's second-conv reads of y1s finished before this tile's ring barriers.
-    const int pt0 = (t0 + tl) * PT;
+    const int pt0 = tile_px(t0 + tl);
     const int co = cob + 8 * (lane >> 4);  // channels co .. co+7
     const int s1 = co >> 6, c1 = (co >> 3) & 7;
     const float nl2e = silu_nl2e();  // act4: the packed form of ycx_act<true>, bit-identical
@@ -2920,11 +2966,11 @@ __global__ void __launch_bounds__(512) conv1x1_wres_pair(ConvArgs a, ConvArgs b)
       eltx8 ov;
 #pragma unroll
       for (int i = 0; i < FM; ++i) {
-        const f32x4 v = act4(acc[i][j] + bv[i], a.act, a.slope, nl2e);
+        const f32x4 v = act4(acc[i][j] + (TRIO ? bias4(0, co + 4 * i) : bv[i]), a.act, a.slope, nl2e);
 #pragma unroll
         for (int q = 0; q < 4; ++q) ov[4 * i + q] = (elt_t)v[q];
       }
-      const int row = j * 16 + (lane & 15), p = pt0 + row;
+      const int row = j * 16 + (lane & 15), p = pt0 + row_px(row);
       if (store1 && p < a.M)
         if (YCX_OUT_OK(a, Y1 + (size_t)p * a.out_cs + co, sizeof(eltx8))) *reinterpret_cast<eltx8*>(Y1 + (size_t)p * a.out_cs + co) = ov;
       *reinterpret_cast<eltx8*>(y1s + s1 * SLAB + row * 128 + ((c1 ^ swz<64>(row)) << 4)) = ov;
@@ -2932,6 +2978,24 @@ __global__ void __launch_bounds__(512) conv1x1_wres_pair(ConvArgs a, ConvArgs b)
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the raw s_barrier does not wait for LDS stores
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
+    if constexpr (TRIO) {
+      // MP's k2 s2 pool of the y1 tile: thread (pc, ch) takes the max of 8 channels over the window
+      // of pooled pixel pc (tile rows 2 pc, 2 pc + 1, 32 + 2 pc, 33 + 2 pc), conv_bf16_glds's POOL
+      // expression in ycx_maxpool's window order. The previous tile's third conv read p1s before
+      // this tile's ring barriers.
+      const int pc = tid & 15, ch = tid >> 4;
+      const char* src = y1s + (ch >> 3) * SLAB + ((((ch & 7) ^ swz<64>(2 * pc))) << 4);  // swz(2 pc + 1) = swz(32 + 2 pc) = swz(2 pc)
+      eltx8 pw[4];
+      pw[0] = *reinterpret_cast<const eltx8*>(src + (2 * pc) * 128);
+      pw[1] = *reinterpret_cast<const eltx8*>(src + (2 * pc + 1) * 128);
+      pw[2] = *reinterpret_cast<const eltx8*>(src + (32 + 2 * pc) * 128);
+      pw[3] = *reinterpret_cast<const eltx8*>(src + (33 + 2 * pc) * 128);
+      eltx8 v;
+#pragma unroll
+      for (int j = 0; j < 8; ++j)
+        v[j] = (elt_t)fmaxf(fmaxf((float)pw[0][j], (float)pw[1][j]), fmaxf((float)pw[2][j], (float)pw[3][j]));
+      *reinterpret_cast<eltx8*>(p1s + (ch >> 3) * P1_SLAB + pc * 128 + (((ch & 7) ^ swz<64>(pc)) << 4)) = v;
+    }
     // second conv on the y1 tile
     f32x4 acc2[FM][FN2];
 #pragma unroll
@@ -2960,15 +3024,57 @@ __global__ void __launch_bounds__(512) conv1x1_wres_pair(ConvArgs a, ConvArgs b)
       eltx8 ov;
 #pragma unroll
       for (int i = 0; i < FM; ++i) {
-        const f32x4 v = act4(acc2[i][j] + bv2[i], b.act, b.slope, nl2e);
+        const f32x4 v = act4(acc2[i][j] + (TRIO ? bias4(256, co2 + 4 * i) : bv2[i]), b.act, b.slope, nl2e);
 #pragma unroll
         for (int q = 0; q < 4; ++q) ov[4 * i + q] = (elt_t)v[q];
       }
-      const int p = pt0 + h2 * 16 * FN2 + j * 16 + (lane & 15);
+      const int p = pt0 + row_px(h2 * 16 * FN2 + j * 16 + (lane & 15));
       if (p < b.M && co2 < b.Cout)
         if (YCX_OUT_OK(b, Y2 + (size_t)p * b.out_cs + co2, sizeof(eltx8))) *reinterpret_cast<eltx8*>(Y2 + (size_t)p * b.out_cs + co2) = ov;
     }
+    if constexpr (TRIO) {
+      // third conv on the pooled tile: every thread's pooled chunk is in LDS after this barrier
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      __builtin_amdgcn_s_barrier();
+      __builtin_amdgcn_sched_barrier(0);
+      f32x4 acc3 = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int kk = 0; kk < K2 / 32; ++kk) {
+        const int ck = (kk & 1) * 4 + (lane >> 4);
+        const eltx8 bfr =
+            *reinterpret_cast<const eltx8*>(p1s + (kk >> 1) * P1_SLAB + m16 * 128 + ((ck ^ swz<64>(m16)) << 4));
+        const eltx8 wf = kk < K3R ? af3[kk < K3R ? kk : 0]
+                                  : *reinterpret_cast<const eltx8*>(w3s + (wid * (K2 / 32 - K3R) + kk - K3R) * 1024 + lane * 16);
+        acc3 = YCX_MFMA16(wf, bfr, acc3, 0, 0, 0);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      const f32x4 v = act4(acc3 + bias4(512, cob3 + 4 * (lane >> 4)), c3.act, c3.slope, nl2e);
+      eltx4 ov;
+#pragma unroll
+      for (int q = 0; q < 4; ++q) ov[q] = (elt_t)v[q];
+      const int tt = t0 + tl, tq = tt / wb;
+      const int p = tq * (a.W >> 1) + 16 * (tt - tq * wb) + m16;  // pooled row tq, column 16 cb + m16
+      const int co3 = cob3 + 4 * (lane >> 4);
+      if (p < c3.M && co3 < c3.Cout)
+        if (YCX_OUT_OK(c3, Y3 + (size_t)p * c3.out_cs + co3, sizeof(eltx4))) *reinterpret_cast<eltx4*>(Y3 + (size_t)p * c3.out_cs + co3) = ov;
+    }
   }
+}
+
+template <int KC, int NS, int SUB, int CO2>
+__global__ void __launch_bounds__(512) conv1x1_wres_pair(ConvArgs a, ConvArgs b) {
+  wres_pair_body<KC, NS, SUB, CO2, false>(a, b, b);
+}
+
+// The pair plus the MP branch's 1x1 (ycx_conv2d_pair_pool): y3 = act(W3 MP2x2(y1) + b3)
+// (256 -> cout_pad 128) from the y1 tile in LDS, so y1 needs no HBM round trip when the
+// max-pool branch is its only other reader (yolov7 layers 11 -> 12 -> 13). Tiles are two
+// image rows x 32 columns (h even, w % 32 == 0), so every pool window lies inside one tile.
+// y3's sum chain is conv_bf16_glds's (ascending 32-wide K chunks): bit-identical to the
+// unfused in_pool conv on the stored y1.
+template <int KC, int NS, int SUB, int CO2>
+__global__ void __launch_bounds__(512) conv1x1_wres_pair_pool(ConvArgs a, ConvArgs b, ConvArgs c) {
+  wres_pair_body<KC, NS, SUB, CO2, true>(a, b, c);
 }
 
 // -------------------------------------------------------------------------
@@ -3357,7 +3463,7 @@ const TileInfo kTiles[] = {
     {128, 256, 64, "retired_glds16w_co128_px256_s2"},
     {256, 128, 64, "retired_glds16w_co256_px128_s3"},
     {128, 256, 64, "retired_glds16w_co128_px256_s3"},
-    {256, 64, 64, "wres1x1_pair"},  // 55: ycx_conv2d_pair only (two chained 1x1 convs)
+    {256, 64, 64, "wres1x1_pair"},  // 55: ycx_conv2d_pair / ycx_conv2d_pair_pool only (chained 1x1 convs)
     {64, 128, 64, "glds_co64_px128_k64_s3"},  // 56: tile 18 with a three-stage ring (r06)
     {128, 128, 64, "retired_wsp_co128_px128_k64_ns4"},  // 57: tools/experiments/wsp_tile57.patch (r06)
 };
@@ -3617,6 +3723,27 @@ ycx_status launch_wres_pair(ConvArgs a, ConvArgs b, hipStream_t st) {
   }
 }
 
+// tile 55 with the MP branch's 1x1 (conv1x1_wres_pair_pool): 2-row x 32-column tiles, all whole
+template <int KC, int NS, int SUB>
+ycx_status launch_wres_pair_pool_k(ConvArgs a, ConvArgs b, ConvArgs c, hipStream_t st) {
+  const int T = a.M / 64;
+  a.nwg = std::max(1, (int)even_grid(T, 256));
+  if (b.Cout_pad == 128)
+    hipLaunchKernelGGL((conv1x1_wres_pair_pool<KC, NS, SUB, 128>), dim3(a.nwg), dim3(512), 0, st, a, b, c);
+  else
+    hipLaunchKernelGGL((conv1x1_wres_pair_pool<KC, NS, SUB, 256>), dim3(a.nwg), dim3(512), 0, st, a, b, c);
+  return ycx_launch_status();
+}
+
+ycx_status launch_wres_pair_pool(ConvArgs a, ConvArgs b, ConvArgs c, hipStream_t st) {
+  switch (a.Cin) {
+    case 64: return launch_wres_pair_pool_k<1, 5, 1>(a, b, c, st);
+    case 128: return launch_wres_pair_pool_k<2, 5, 2>(a, b, c, st);
+    case 256: return launch_wres_pair_pool_k<4, YCX_WRES_NS, 2>(a, b, c, st);
+    default: return YCX_ERR_UNSUPPORTED;
+  }
+}
+
 bool wres_f8_ok(const ConvArgs& a) {
   return a.KH == 1 && a.KW == 1 && a.S == 1 && a.P == 0 && a.H == a.Ho && a.W == a.Wo && !a.res &&
          a.out_layout == YCX_OUT_NHWC && (a.Cin == 128 || a.Cin == 256 || a.Cin == 512) && a.Ktot == a.Cin &&
@@ -3811,6 +3938,9 @@ extern "C" ycx_status ycx_stem_conv_f16(const ycx_conv_desc*, const float*, cons
                                         void*);
 extern "C" ycx_status ycx_conv2d_pair_f16(const ycx_conv_desc*, const ycx_conv_desc*, const void*, const void*,
                                           const float*, void*, const void*, const float*, void*, void*);
+extern "C" ycx_status ycx_conv2d_pair_pool_f16(const ycx_conv_desc*, const ycx_conv_desc*, const ycx_conv_desc*,
+                                               const void*, const void*, const float*, void*, const void*,
+                                               const float*, void*, const void*, const float*, void*, void*);
 extern "C" ycx_status ycx_stem_conv2_f16(const ycx_conv_desc*, const ycx_conv_desc*, const float*, const float*,
                                          const float*, const void*, const float*, void*, void*);
 #define YCX_TO_F16(cond, call) \
@@ -4012,6 +4142,44 @@ extern "C" ycx_status YCX_SFX(ycx_conv2d_pair)(const ycx_conv_desc* da, const yc
   ConvArgs a = make_args(da, x, wa, ba, ya, nullptr);
   ConvArgs b = make_args(db, nullptr, wb, bb, yb, nullptr);
   return launch_wres_pair(a, b, reinterpret_cast<hipStream_t>(stream));
+}
+
+extern "C" ycx_status YCX_SFX(ycx_conv2d_pair_pool)(const ycx_conv_desc* da, const ycx_conv_desc* db,
+                                                    const ycx_conv_desc* dc, const void* x, const void* wa,
+                                                    const float* ba, void* ya, const void* wb, const float* bb,
+                                                    void* yb, const void* wc, const float* bc, void* yc,
+                                                    void* stream) {
+  YCX_TO_F16(da && da->dtype == YCX_DT_F16,
+             ycx_conv2d_pair_pool_f16(da, db, dc, x, wa, ba, ya, wb, bb, yb, wc, bc, yc, stream));
+  YCX_CHECK_ARG(da && db && dc && x && wa && ba && wb && bb && yb && wc && bc && yc);
+  YCX_CHECK_ARG(da->n > 0 && da->h > 0 && da->w > 0 && da->cin > 0 && da->cout > 0);
+  YCX_CHECK_ARG(da->ho == da->h && da->wo == da->w && db->n == da->n && db->h == da->ho && db->w == da->wo &&
+                db->ho == db->h && db->wo == db->w && db->cin == da->cout && db->cout > 0);
+  YCX_CHECK_ARG(da->in_c_off >= 0 && da->in_c_off + da->cin <= da->in_c_stride && db->cout_pad >= db->cout);
+  YCX_CHECK_ARG(db->out_c_off >= 0 && db->out_c_off + db->cout <= db->out_c_stride);
+  YCX_CHECK_ARG(!ya || (da->out_c_off >= 0 && da->out_c_off + da->cout <= da->out_c_stride));
+  YCX_CHECK_ARG(dc->n == da->n && dc->ho == dc->h && dc->wo == dc->w && dc->cout > 0 && dc->cout_pad >= dc->cout);
+  YCX_CHECK_ARG(dc->out_c_off >= 0 && dc->out_c_off + dc->cout <= dc->out_c_stride);
+  YCX_CHECK_SUPPORTED(da->dtype == YCX_DT_ELT && db->dtype == YCX_DT_ELT && dc->dtype == YCX_DT_ELT);
+  for (const ycx_conv_desc* d : {da, db, dc}) {
+    YCX_CHECK_SUPPORTED(d->kh == 1 && d->kw == 1 && d->stride == 1 && d->pad == 0 &&
+                        d->out_layout == YCX_OUT_NHWC && d->act >= YCX_ACT_NONE && d->act <= YCX_ACT_SILU_PS);
+    YCX_CHECK_SUPPORTED(d->out_c_off % 8 == 0 && d->out_c_stride % 8 == 0);
+  }
+  YCX_CHECK_SUPPORTED(!da->in_pool && !db->in_pool);
+  YCX_CHECK_SUPPORTED((da->cin == 64 || da->cin == 128 || da->cin == 256) && da->cout == 256 && da->cout_pad == 256);
+  YCX_CHECK_SUPPORTED(da->in_c_off % 8 == 0 && da->in_c_stride % 8 == 0);
+  YCX_CHECK_SUPPORTED(db->cin == 256 && (db->cout_pad == 128 || db->cout_pad == 256) && db->cout % 8 == 0);
+  YCX_CHECK_SUPPORTED((long long)da->n * da->h * da->w * da->in_c_stride * 2 < (1LL << 31) - 64);
+  // the MP branch: c reads the k2 s2 max-pool of a's output; tiles of two rows x 32 columns
+  YCX_CHECK_SUPPORTED(dc->in_pool == 1);
+  YCX_CHECK_SUPPORTED(da->h % 2 == 0 && da->w % 32 == 0);
+  YCX_CHECK_SUPPORTED(dc->h == da->h / 2 && dc->w == da->w / 2);
+  YCX_CHECK_SUPPORTED(dc->cin == 256 && dc->cout_pad == 128 && dc->cout % 8 == 0);
+  ConvArgs a = make_args(da, x, wa, ba, ya, nullptr);
+  ConvArgs b = make_args(db, nullptr, wb, bb, yb, nullptr);
+  ConvArgs c = make_args(dc, nullptr, wc, bc, yc, nullptr);
+  return launch_wres_pair_pool(a, b, c, reinterpret_cast<hipStream_t>(stream));
 }
 
 extern "C" ycx_status YCX_SFX(ycx_stem_conv)(const ycx_conv_desc* d, const float* x, const float* w,

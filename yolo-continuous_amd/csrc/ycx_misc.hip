@@ -434,6 +434,9 @@ static ycx_status run_one(const ycx_op& op, void* stream) {
       return ycx_stem_conv2(&op.d.pair[0], &op.d.pair[1], (const float*)op.in, (const float*)op.weight, op.bias,
                             op.weight2, op.bias2, op.out, stream);
     case YCX_OP_CONV_PAIR:
+      if (op.out3)
+        return ycx_conv2d_pair_pool(&op.d.pair[0], &op.d.pair[1], &op.conv3, op.in, op.weight, op.bias, op.out,
+                                    op.weight2, op.bias2, op.out2, op.weight3, op.bias3, op.out3, stream);
       return ycx_conv2d_pair(&op.d.pair[0], &op.d.pair[1], op.in, op.weight, op.bias, op.out, op.weight2, op.bias2,
                              op.out2, stream);
     case YCX_OP_HEAD:

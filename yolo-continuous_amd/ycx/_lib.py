@@ -98,7 +98,9 @@ class Op(ctypes.Structure):
                 ("out", ctypes.c_void_p), ("residual", ctypes.c_void_p),
                 ("weight2", ctypes.c_void_p), ("bias2", ctypes.c_void_p),
                 ("cand", ctypes.c_void_p), ("cand_rows", ctypes.c_void_p), ("cand_counts", ctypes.c_void_p),
-                ("status", ctypes.c_void_p), ("out2", ctypes.c_void_p), ("workspace", ctypes.c_void_p)]
+                ("status", ctypes.c_void_p), ("out2", ctypes.c_void_p), ("workspace", ctypes.c_void_p),
+                ("conv3", ConvDesc), ("weight3", ctypes.c_void_p), ("bias3", ctypes.c_void_p),
+                ("out3", ctypes.c_void_p)]
 
 
 class LetterboxDesc(ctypes.Structure):
@@ -137,6 +139,8 @@ _SIGS = [
                               _VP]),
     ("ycx_conv2d_pair", _i32, [ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _VP, _VP, _VP,
                                _VP, _VP]),
+    ("ycx_conv2d_pair_pool", _i32, [ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc),
+                                    _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("ycx_maxpool", _i32, [ctypes.POINTER(PoolDesc), _VP, _VP, _VP]),
     ("ycx_copy_channels", _i32, [ctypes.POINTER(CopyDesc), _VP, _VP, _VP]),
     ("ycx_quantize_fp8", _i32, [_VP, _VP, ctypes.c_int64, ctypes.c_float, _VP]),

@@ -462,7 +462,7 @@ class Engine:
     """A compiled plan bound to device memory for one (input shape, device, precision)."""
 
     def __init__(self, model, shape, device, precision='bf16', fuse_stem2=True, fp8_amax=None, prepacked=None,
-                 fuse_pool=True, fuse_pair=True):
+                 fuse_pool=True, fuse_pair=True, fuse_pair_pool=True):
         if device.type != 'cuda':
             raise RuntimeError("ycx: the HIP path needs the model input on a ROCm device (tensor.to('cuda')); "
                                "there is no CPU path")
@@ -474,6 +474,7 @@ class Engine:
         self.fuse_stem2 = fuse_stem2
         self.fuse_pool = fuse_pool  # False: every pool writes its map (fp8 calibration reads them all)
         self.fuse_pair = fuse_pair  # False: every 1x1 of a pair stores its map (fp8 calibration reads them all)
+        self.fuse_pair_pool = fuse_pair_pool  # False: a pair stores its first map for the MP branch's pooled 1x1
         self.prepacked = prepacked  # {'p<i>': packed tensor} from ycx.prepack (skips folding / packing)
         self.graph_exec = None
         self.graph, self.out_vals, self.is_list = self.plan.graph, self.plan.out_vals, self.plan.is_list
@@ -616,8 +617,37 @@ class Engine:
                 break
         return out
 
-    def _pair_op(self, a, b):
-        """One OP_CONV_PAIR for the chain a -> b (``_conv_pairs``)."""
+    def _pair_pools(self, chains, pooled):
+        """Pairs (``_conv_pairs``) that also run the MP branch's 1x1 (ycx_conv2d_pair_pool): the
+        first conv's only other reader is a k2 s2 max-pool already fused into its 1x1 conv c
+        (``_pool_convs``), c is 256 -> cout_pad 128 with an NHWC output on 8-channel bounds, and the
+        map is h even, w % 32 == 0 (yolov7: layer 11 -> 14 with 12 -> 13). The 256-channel map is then
+        neither stored nor read back. Off with the pair, or with ``fuse_pair_pool=False``.
+        Returns {id(first conv): (pooled conv c, its pool node)}."""
+        out = {}
+        if not self.fuse_pair_pool:
+            return out
+        by_pool = {id(pl): c for c, pl in ((c, pooled[id(c)]) for c in self.graph.nodes if id(c) in pooled)}
+        for a in self.graph.nodes:
+            b = chains.get(id(a))
+            if b is None:
+                continue
+            v = a.out
+            rest = [nd for nd in v.consumers if nd is not b]
+            if len(rest) != 1 or id(rest[0]) not in by_pool or v.role != 'act' or v.h % 2 or v.w % 32:
+                continue
+            c = by_pool[id(rest[0])]
+            q, cc = c.p, int(c.p['w'].shape[0])
+            if int(q['w'].shape[1]) != 256 or self._cout_pad(cc) != 128 or cc % 8 or q['residual'] is not None:
+                continue
+            if q['layout'] != L.OUT_NHWC or c.out.role != 'act' or c.out.coff % 8 or c.out.buf.c % 8:
+                continue
+            out[id(a)] = (c, rest[0])
+        return out
+
+    def _pair_op(self, a, b, c=None, pool=None):
+        """One OP_CONV_PAIR for the chain a -> b (``_conv_pairs``); with c (``_pair_pools``) also the
+        1x1 conv on the max-pool of a's output."""
         da, wa, ba, fa, shape = self._conv_parts(a)
         db, wb, bb, fb, _ = self._conv_parts(b)
         op = L.Op()
@@ -625,16 +655,26 @@ class Engine:
         op.d.pair[0], op.d.pair[1] = da, db
         idx = len(self.op_info)
         v = a.out
-        store_a = len(v.consumers) > 1
+        store_a = len(v.consumers) > 1 and c is None
         op.in_ = self._val_ptr(a.inputs[0], idx, 'in_')
         op.weight, op.bias = wa.data_ptr(), ba.data_ptr()
         op.weight2, op.bias2 = wb.data_ptr(), bb.data_ptr()
         op.out = self._val_ptr(v, idx, 'out') if store_a else None
         op.out2 = self._val_ptr(b.out, idx, 'out2')
+        isz = self.dtype.itemsize
         nbytes = (self._conv_bytes(da, wa, out_bytes=store_a) +
-                  self._conv_bytes(db, wb) - db.n * db.h * db.w * db.cin * self.dtype.itemsize)  # y1 stays on chip
-        self.op_info.append(dict(kind='conv_pair', name='wres1x1_pair', flops=fa + fb, shape=shape, parts=2,
-                                 shape2=(db.n, db.h, db.w, db.cin, db.cout, 1, 1), bytes=nbytes))
+                  self._conv_bytes(db, wb) - db.n * db.h * db.w * db.cin * isz)  # y1 stays on chip
+        info = dict(kind='conv_pair', name='wres1x1_pair', flops=fa + fb, shape=shape, parts=2,
+                    shape2=(db.n, db.h, db.w, db.cin, db.cout, 1, 1))
+        if c is not None:
+            dc, wc, bc, fc, _ = self._conv_parts(c, pool=pool)
+            op.conv3 = dc
+            op.weight3, op.bias3 = wc.data_ptr(), bc.data_ptr()
+            op.out3 = self._val_ptr(c.out, idx, 'out3')
+            nbytes += self._conv_bytes(dc, wc, pooled=True) - 4 * dc.n * dc.h * dc.w * dc.cin * isz  # nor is it read back
+            info.update(name='wres1x1_pair+mp_conv', flops=fa + fb + fc, parts=3,
+                        shape3=(dc.n, dc.h, dc.w, dc.cin, dc.cout, 1, 1))
+        self.op_info.append(dict(info, bytes=nbytes))
         return op
 
     def _build(self):
@@ -661,6 +701,8 @@ class Engine:
         fused.update(id(nd) for nd in pooled.values())
         chains = self._conv_pairs(pooled)  # {id(first 1x1): second 1x1} (one launch each)
         fused.update(id(nd) for nd in chains.values())
+        trios = self._pair_pools(chains, pooled)  # {id(first 1x1): (pooled 1x1, pool)} (in the pair's launch)
+        fused.update(id(c) for c, _ in trios.values())
         for node in self.graph.nodes:
             k = node.kind
             if id(node) in fused:
@@ -668,7 +710,7 @@ class Engine:
             if id(node) in pairs:
                 ops.append(self._stem2_op(node, pairs[id(node)]))
             elif id(node) in chains:
-                ops.append(self._pair_op(node, chains[id(node)]))
+                ops.append(self._pair_op(node, chains[id(node)], *trios.get(id(node), ())))
             elif k in ('conv', 'stem'):
                 ops.append(self._conv_op(node, pool=pooled.get(id(node))))
             elif k == 'pool':
