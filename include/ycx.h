@@ -17,6 +17,7 @@
  *   ycx_stem_conv2      first two Convs fused (3->32, then 3x3   cfg/net/yolov7.yaml:7-8,
  *                       stride 2 -> 64); the stem output stays   nets/common.py:97-109
  *                       in LDS
+ *   ycx_stem_conv_reorg ReOrg + the Conv that reads it (P6 stems)   nets/common.py:43-51, 97-109
  *   ycx_maxpool         MP / SP / SPPCSPC max-pools             nets/common.py:25-40, 257
  *   ycx_copy_channels   nn.Upsample(None, 2, 'nearest')         cfg/net/yolov7.yaml:71,85
  *                       Concat (only when a slice cannot alias)  nets/common.py:54-60
@@ -212,7 +213,8 @@ typedef struct ycx_head_desc {
 
 /* A pre-built op for ycx_run_ops (the static execution plan of Model.forward). */
 enum { YCX_OP_CONV = 1, YCX_OP_STEM = 2, YCX_OP_POOL = 3, YCX_OP_COPY = 4, YCX_OP_STEM2 = 5, YCX_OP_HEAD = 6,
-       YCX_OP_CONV_PAIR = 7 };
+       YCX_OP_CONV_PAIR = 7,
+       YCX_OP_STEM_REORG = 8 /* ycx_stem_conv_reorg: d.conv, in, weight, bias, out */ };
 typedef struct ycx_op {
   int32_t kind;
   int32_t pad_;
@@ -328,6 +330,18 @@ ycx_status ycx_stem_conv(const ycx_conv_desc* d, const float* x, const float* w,
 ycx_status ycx_stem_conv2(const ycx_conv_desc* stem, const ycx_conv_desc* conv, const float* x,
                           const float* w_stem, const float* b_stem, const void* w_conv,
                           const float* b_conv, void* y, void* stream);
+/* First Conv of a network whose layer 0 is ReOrg (nets/common.py:43-51, then :97-109): the
+ * space-to-depth is done in the operand gather, the 4C-channel map never exists in memory
+ * (a 3x3 / s / pad-1 conv over ReOrg(x) is a 6x6 / 2s / pad-2 conv over x).
+ * x: fp32 NCHW image [n][C][2h][2w] (8-byte aligned), C = d->in_c_stride <= 4, d->in_c_off == 0.
+ * d describes the conv as the reference sees it AFTER ReOrg: d->h, d->w the reorganised map,
+ * d->cin == 4*C, kh == kw == 3, pad 1, stride 1 or 2.
+ * w: fp32 [kh][kw][cin][cout_pad], cin in ReOrg's channel order q*C + c with
+ *    q = 0 (even row, even col), 1 (odd row, even col), 2 (even row, odd col), 3 (odd row, odd col).
+ * y, dtype, act, out_c_*, out_scale: as ycx_stem_conv (bf16 / fp16 / f32 / fp8 output, NHWC;
+ * cout_pad 32 or a multiple of 64; f32: the exact fp32 FMA chain of the parity mode). */
+ycx_status ycx_stem_conv_reorg(const ycx_conv_desc* d, const float* x, const float* w,
+                               const float* bias, void* y, void* stream);
 ycx_status ycx_maxpool(const ycx_pool_desc* d, const void* x, void* y, void* stream);
 ycx_status ycx_copy_channels(const ycx_copy_desc* d, const void* x, void* y, void* stream);
 /* fp32 -> OCP e4m3fn bytes: y[i] = e4m3(clamp(x[i] * scale, +-448)), round to

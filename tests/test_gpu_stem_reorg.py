@@ -1,0 +1,238 @@
+"""ycx_stem_conv_reorg (ReOrg folded into the first conv) on exactly representable operands.
+
+The exact-operand method of tests/test_gpu_conv_exact.py: image in 1/32 steps within +-4, weights in
+1/32 steps within +-2 (both exact in bf16 and fp16), bias in 1/16 steps within +-2. K = 36 C <= 108
+terms of at most 128 * 64 units of 2^-10: the span 108 * 128 * 64 = 884,736 < 2^20, so the fp32
+accumulator holds the true sum whatever the K order and the stored element must be RNE(true sum).
+The reference is torch's float64 conv2d over reorg(x), reorg being four strided slices and a cat
+(nets/common.py:51). Every 16-bit case asserts from the reference alone that >= 10 % of its outputs
+need rounding and >= 1 % are ties; the fp32 case that the cast is lossless.
+
+Shapes (reorganised maps, n = 2): 9 x 11 (every border, a ragged pixel tail), 16 x 32, 8 x 64 (a full
+MFMA row); stride 1 and 2; cout 32 and 64, 48 padded to 64; C = 3 and 1; output channel slice at 8."""
+import ctypes
+import functools
+import types
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from helpers import dyadic, elt_neighbours, elt_ulps, rne, rounding_stats
+
+pytestmark = pytest.mark.gpu
+
+L = pytest.importorskip("ycx._lib")
+
+TDT = {L.DT_BF16: torch.bfloat16, L.DT_F16: torch.float16, L.DT_F32: torch.float32}
+SPAN = 1 << 20
+MIN_ROUNDED, MIN_TIES = 0.10, 0.01
+ACTS = [(L.ACT_NONE, 0.0), (L.ACT_LEAKY, 0.125), (L.ACT_LEAKY, 0.25)]
+X_MAX, X_STEP, W_MAX, W_STEP, B_MAX, B_STEP = 4.0, 1 / 32, 2.0, 1 / 32, 2.0, 1 / 16
+OUT_EXTRA = 8
+SHAPES = [(9, 11), (16, 32), (8, 64)]
+assert 108 * (X_MAX / X_STEP) * (W_MAX / W_STEP) == 884736 < SPAN
+
+
+def reorg(x):
+    return torch.cat([x[..., ::2, ::2], x[..., 1::2, ::2], x[..., ::2, 1::2], x[..., 1::2, 1::2]], 1)
+
+
+@functools.lru_cache(maxsize=None)
+def operands(h, w, s, c=3, grid=(X_STEP, W_STEP, X_MAX, W_MAX, B_MAX), seed=0):
+    """Image [2][c][2h][2w], weights [64][4c][3][3], bias [64] (float64, never modified) and the exact
+    pre-activation z of the conv over reorg(x), shared by every dtype / act / cout that runs it."""
+    sx, sw, xm, wm, bm = grid
+    assert 36 * c * (xm / sx) * (wm / sw) < SPAN
+    g = torch.Generator().manual_seed(7919 * seed + 31 * h + w + 1000 * s + c)
+    o = types.SimpleNamespace(n=2, h=h, w=w, s=s, c=c)
+    o.x = dyadic((2, c, 2 * h, 2 * w), -xm, xm, sx, g)
+    o.wt = dyadic((64, 4 * c, 3, 3), -wm, wm, sw, g)
+    o.b = dyadic((64,), -bm, bm, B_STEP, g)
+    for t in (o.x, o.wt):
+        assert torch.equal(t.to(torch.bfloat16).double(), t) and torch.equal(t.to(torch.float16).double(), t)
+    o.z = F.conv2d(reorg(o.x), o.wt, o.b, s, 1)
+    o.ho, o.wo = o.z.shape[2:]
+    return o
+
+
+def apply_act(z, act, slope):
+    return torch.where(z > 0, z, z * slope) if act == L.ACT_LEAKY else z
+
+
+def check_inputs(ref64, tdt, what=""):
+    if tdt == torch.float32:
+        assert torch.equal(ref64.float().double(), ref64), "fp32 does not hold the exact sums"
+        return
+    rounded, ties = rounding_stats(ref64, tdt)
+    assert rounded >= MIN_ROUNDED and ties >= MIN_TIES, \
+        f"{what}: inputs too easy, {rounded:.3f} of the outputs need rounding, {ties:.3f} are ties"
+
+
+def assert_bits(got, exp, what=""):
+    it = torch.int32 if got.dtype == torch.float32 else torch.int16
+    assert got.shape == exp.shape and got.dtype == exp.dtype
+    if torch.equal(got.contiguous().view(it), exp.contiguous().view(it)):
+        return
+    bad = got.contiguous().view(it) != exp.contiguous().view(it)
+    d = elt_ulps(got, exp, got.dtype)[bad]
+    raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements differ from RNE(true sum); "
+                         f"distance in representable values: min {int(d.min())}, max {int(d.max())}; "
+                         f"first at {[int(v) for v in bad.nonzero()[0]]}")
+
+
+def cpad_of(cout, dtype):
+    return -(-cout // 64) * 64 if dtype == L.DT_F32 else (32 if cout <= 32 else -(-cout // 64) * 64)
+
+
+def launch(device, o, dtype, cout, act=L.ACT_NONE, slope=0.0, cpad=None, out_scale=1.0, via_ops=False):
+    """One call through the C ABI (or as a YCX_OP_STEM_REORG through ycx_run_ops); the raw output buffer."""
+    cpad = cpad or cpad_of(cout, dtype)
+    wp = torch.zeros(3, 3, 4 * o.c, cpad)
+    wp[..., :cout] = o.wt[:cout].permute(2, 3, 1, 0).float()
+    bp = torch.zeros(cpad)
+    bp[:cout] = o.b[:cout].float()
+    ydt = torch.uint8 if dtype == L.DT_FP8 else TDT[dtype]
+    d = L.ConvDesc()
+    d.n, d.h, d.w, d.cin, d.in_c_off, d.in_c_stride = o.n, o.h, o.w, 4 * o.c, 0, o.c
+    d.ho, d.wo, d.cout, d.cout_pad, d.out_c_off, d.out_c_stride = o.ho, o.wo, cout, cpad, OUT_EXTRA, cout + OUT_EXTRA
+    d.kh = d.kw = 3
+    d.stride, d.pad, d.act, d.leaky_slope, d.dtype, d.out_layout = o.s, 1, act, slope, dtype, L.OUT_NHWC
+    d.out_scale = out_scale
+    xd, wd, bd = o.x.float().to(device), wp.to(device), bp.to(device)
+    yd = torch.zeros(o.n, o.ho, o.wo, cout + OUT_EXTRA, dtype=ydt, device=device)
+    st = L.stream_handle(device)
+    if via_ops:
+        op = L.Op()
+        op.kind = L.OP_STEM_REORG
+        op.d.conv = d
+        op.in_, op.weight, op.bias, op.out = xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), yd.data_ptr()
+        L.check(L.lib.ycx_run_ops(ctypes.byref(op), 1, st, None), "ycx_run_ops")
+    else:
+        L.check(L.lib.ycx_stem_conv_reorg(ctypes.byref(d), xd.data_ptr(), wd.data_ptr(), bd.data_ptr(),
+                                          yd.data_ptr(), st), "ycx_stem_conv_reorg")
+    torch.cuda.synchronize()
+    return yd.cpu()
+
+
+def expected(ref64, tdt):
+    r = ref64.permute(0, 2, 3, 1)
+    exp = torch.zeros(*r.shape[:3], r.shape[3] + OUT_EXTRA, dtype=tdt)
+    exp[..., OUT_EXTRA:] = rne(r, tdt)
+    return exp
+
+
+def run_acts(device, o, dtype, cout, what, cpad=None):
+    tdt = TDT[dtype]
+    for act, slope in ACTS:
+        ref = apply_act(o.z[:, :cout], act, slope)
+        check_inputs(ref, tdt, what)
+        got = launch(device, o, dtype, cout, act, slope, cpad=cpad)
+        assert_bits(got, expected(ref, tdt), f"{what} act {act} slope {slope}")
+
+
+@pytest.mark.parametrize('dtype', [L.DT_BF16, L.DT_F16, L.DT_F32])
+@pytest.mark.parametrize('cout', [32, 64])
+@pytest.mark.parametrize('s', [1, 2])
+@pytest.mark.parametrize('h,w', SHAPES)
+def test_exact_stem_reorg(device, h, w, s, cout, dtype):
+    run_acts(device, operands(h, w, s), dtype, cout, f"stem_reorg {h}x{w} s{s} cout {cout} dtype {dtype}")
+
+
+@pytest.mark.parametrize('dtype', [L.DT_BF16, L.DT_F16, L.DT_F32])
+def test_exact_stem_reorg_cout_below_pad(device, dtype):
+    """cout 48 in a 64-channel pad: channels 48..63 of the pad are computed and never stored."""
+    run_acts(device, operands(9, 11, 1), dtype, 48, f"stem_reorg cout 48/64 dtype {dtype}", cpad=64)
+
+
+@pytest.mark.parametrize('dtype', [L.DT_BF16, L.DT_F16, L.DT_F32])
+@pytest.mark.parametrize('s', [1, 2])
+def test_exact_stem_reorg_one_channel(device, s, dtype):
+    """C = 1 (a grey image): 4 reorganised channels, K = 36 in two MFMA steps."""
+    run_acts(device, operands(9, 11, s, c=1), dtype, 32, f"stem_reorg C1 s{s} dtype {dtype}")
+
+
+@pytest.mark.parametrize('dtype', [L.DT_BF16, L.DT_F16, L.DT_F32])
+@pytest.mark.parametrize('s', [1, 2])
+def test_op_stem_reorg_matches_direct_call(device, s, dtype):
+    o = operands(9, 11, s)
+    a = launch(device, o, dtype, 64, L.ACT_LEAKY, 0.125)
+    b = launch(device, o, dtype, 64, L.ACT_LEAKY, 0.125, via_ops=True)
+    it = torch.int32 if dtype == L.DT_F32 else torch.int16
+    assert torch.equal(a.view(it), b.view(it))
+    assert_bits(a, expected(apply_act(o.z, L.ACT_LEAKY, 0.125), TDT[dtype]), "direct")
+
+
+# ---- e4m3 store: the bar tests/test_gpu_fp8.py holds a conv's e4m3 output to (>= 99.5 % of the bytes
+# identical to torch's cast of the float64 reference, every other byte one code away) ----
+E4M3 = torch.float8_e4m3fn
+
+
+def codes_close(got_u8, ref_u8):
+    g, r = got_u8.to(torch.int32), ref_u8.to(torch.int32)
+    same = g == r
+    mag_g, mag_r = g & 0x7F, r & 0x7F
+    near = same | (((g ^ r) & 0x80) == 0) & ((mag_g - mag_r).abs() <= 1) | ((mag_g <= 1) & (mag_r <= 1))
+    return float(same.float().mean()), bool(near.all())
+
+
+@pytest.mark.parametrize('s', [1, 2])
+@pytest.mark.parametrize('h,w,cout', [(9, 11, 64), (8, 64, 32)])
+def test_stem_reorg_fp8_store(device, h, w, cout, s):
+    o = operands(h, w, s)
+    so = 4.0  # |z| reaches ~120: the +-448 clamp is exercised too
+    for act, slope in ACTS[:2]:
+        ref = apply_act(o.z[:, :cout], act, slope).permute(0, 2, 3, 1)
+        got = launch(device, o, L.DT_FP8, cout, act, slope, out_scale=so)
+        assert not got[..., :OUT_EXTRA].any(), "wrote outside the output channel slice"
+        ref_q = (ref.float() * so).clamp(-448.0, 448.0).to(E4M3).view(torch.uint8)
+        frac, near = codes_close(got[..., OUT_EXTRA:], ref_q)
+        print(f"\nstem_reorg fp8 {h}x{w} s{s} act {act}: {frac:.5f} of the bytes identical")
+        assert near and frac >= 0.995, (frac, near)
+
+
+# ---- SiLU and pre-scaled SiLU at ulp level: check_silu of tests/test_gpu_conv_exact.py restated ----
+LOG2E = 1.4426950408889634
+SILU_MAX_Z = 32.0
+MAX_EXCUSED = {torch.bfloat16: 0.01, torch.float16: 0.05}
+
+
+def silu_ref(z, act):
+    if act == L.ACT_SILU_PS:  # z = -log2(e) c: c / (1 + 2^z)
+        return (-z / LOG2E) / (1 + torch.exp2(z))
+    return z / (1 + torch.exp(-z))
+
+
+def check_silu(got, z, act, tdt, what):
+    """Bit-exact where the float64 reference lies farther than (|z| + 8) 2^-23 relative from a rounding
+    boundary, within one element-ulp of RNE(reference) everywhere (fp16 subnormals: 2^-24 absolute)."""
+    assert float(z.abs().max()) <= SILU_MAX_Z, "input condition: |z| <= 32"
+    zz = z.permute(0, 2, 3, 1).contiguous()
+    ref = silu_ref(zz, act)
+    lo, hi = elt_neighbours(ref, tdt)
+    margin = (zz.abs() + 8) * 2.0 ** -23 * ref.abs()
+    excused = (lo != hi) & ((ref - (lo + hi) / 2).abs() <= margin)
+    sub = (ref.abs() < 2.0 ** -14) if tdt == torch.float16 else torch.zeros_like(excused)
+    share = float((excused & ~sub).double().mean())
+    assert share <= MAX_EXCUSED[tdt], f"{what}: input condition, {share:.4f} of the elements are excused"
+    assert not got[..., :OUT_EXTRA].any(), "wrote outside the output channel slice"
+    g = got[..., OUT_EXTRA:].contiguous()
+    ulps = elt_ulps(g, rne(ref, tdt), tdt)
+    if sub.any():
+        assert float((g.double() - ref).abs()[sub].max()) <= 2.0 ** -24, what
+    assert int(ulps[~sub].abs().max()) <= 1, f"{what}: {int(ulps[~sub].abs().max())} element-ulps from RNE(ref)"
+    must = ~excused & ~sub
+    bad = must & (ulps != 0)
+    assert not bad.any(), f"{what}: {int(bad.sum())} of {int(must.sum())} elements away from a rounding " \
+                          f"boundary differ from RNE(ref) ({share:.4f} excused, {int(sub.sum())} subnormal)"
+
+
+@pytest.mark.parametrize('act', [L.ACT_SILU, L.ACT_SILU_PS])
+@pytest.mark.parametrize('dtype', [L.DT_BF16, L.DT_F16])
+@pytest.mark.parametrize('s', [1, 2])
+def test_silu_ulps_stem_reorg(device, s, dtype, act):
+    """x and w in 1/8 steps within +-1 (K = 108: hx = 2^floor(log2(12 / sqrt(K))) = 1), bias in 1/16 steps
+    within +-1: z of a few units. YCX_ACT_SILU_PS: the weights and bias themselves are on the grid."""
+    o = operands(9, 11, s, grid=(1 / 8, 1 / 8, 1.0, 1.0, 1.0), seed=3)
+    got = launch(device, o, dtype, 64, act, 0.0)
+    check_silu(got, o.z, act, TDT[dtype], f"stem_reorg s{s} dtype {dtype} act {act}")

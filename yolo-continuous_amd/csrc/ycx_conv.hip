@@ -2305,6 +2305,228 @@ __global__ void __launch_bounds__(256) stem_mfma(ConvArgs a) {
 }
 
 // -------------------------------------------------------------------------
+// ReOrg stem (P6 networks): layer 0 is ReOrg (nets/common.py:43-51), the
+// space-to-depth x(b, C, 2h, 2w) -> (b, 4C, h, w), and layer 1 a 3x3 / pad-1 Conv
+// over it. The 4C-channel map is never built: a 3x3/s conv over ReOrg(x) is a
+// 6x6 / stride-2s / pad-2 conv over x with the weights permuted, and the
+// space-to-depth happens while the image patch of a tile is staged into LDS.
+//
+// Persistent 256-thread blocks walk TH x 64 output tiles (down a column strip:
+// the halo rows a tile shares with the one above were fetched by the same block).
+// Per tile:
+//  (0) the fp32 image rows under the tile are read as coalesced float2 (an even /
+//      odd column pair), converted to the element type once and written as one
+//      dword into the LDS patch [row][col][4C] of reorganised pixels, channel
+//      order (row parity, c, column parity): 4C elements = 8C bytes per pixel;
+//  (1) the three pixels of one tap row (ky; kx = 0..2) of an output pixel are
+//      12C contiguous elements, so the GEMM K axis is k = ky * 8 RC + e with
+//      RC = ceil(12C / 8) 16-byte chunks per tap row: K = 24 RC, for RGB
+//      3 * 40 = 120 of the 128 that four 16x16x32 MFMA steps take (zero weights
+//      in the slack, which the B side masks to zero as well). A lane's B
+//      fragment of a step is one 16-byte LDS read (8-byte aligned: two b64);
+//  (2) A = the folded weights, permuted into that K order and converted once per
+//      block into registers; epilogue and store as stem_mfma (16 bytes per lane,
+//      a pixel's channels contiguous).
+// -------------------------------------------------------------------------
+template <int C>
+struct ReorgGeom {
+  static constexpr int PIX = 4 * C;              // elements per reorganised pixel
+  static constexpr int ROW = 3 * PIX;            // one tap row: three pixels, contiguous in LDS
+  static constexpr int RC = (ROW + 7) / 8;       // 8-element chunks per tap row (ROW % 8 is 0 or 4)
+  static constexpr int NCH = 3 * RC;             // chunks of the K axis
+  static constexpr int NSTEP = (NCH + 3) / 4;    // 32-deep MFMA steps (RGB: 4, K = 128)
+};
+constexpr int kRoTW = 64;                        // output columns of a tile
+typedef __attribute__((ext_vector_type(2))) elt_t eltx2;
+typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+
+template <int C, int S, int CT, bool F8 = false>  // image channels, conv stride, 16-channel MFMA rows, e4m3 output
+__global__ void __launch_bounds__(256) stem_reorg_mfma(ConvArgs a) {
+  using G = ReorgGeom<C>;
+  constexpr int PIX = G::PIX, ROW = G::ROW, RC = G::RC, NCH = G::NCH, NSTEP = G::NSTEP;
+  constexpr int TH = 8 / S, TW = kRoTW;
+  constexpr int PR = (TH - 1) * S + 3, PW = (TW - 1) * S + 3;  // reorganised pixels under a tile
+  constexpr int NELT = PR * PW * PIX;
+  // + 8: the last chunk of the last pixel's tap row reads (and masks) four elements past it
+  __shared__ __attribute__((aligned(16))) elt_t patch[NELT + 8];
+  const int tid = threadIdx.x, lane = tid & 63, lx = lane & 15, kq = lane >> 4;
+  const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const float* Wt = reinterpret_cast<const float*>(a.w);  // [3][3][4C][Cout_pad], channel q * C + c
+  const float* __restrict__ X = reinterpret_cast<const float*>(a.x);
+  const int co_base = blockIdx.y * 16 * CT;
+  eltx8 af[NSTEP][CT];
+  int koff[NSTEP];
+  uint32_t lmask[NSTEP], hmask[NSTEP];  // a chunk past K reads as zeros; so do the four elements past a tap row
+#pragma unroll
+  for (int st = 0; st < NSTEP; ++st) {
+    const int ch = 4 * st + kq;
+    const bool cv = ch < NCH;
+    const int ky = cv ? ch / RC : 0, i = cv ? ch - ky * RC : 0;
+    koff[st] = ky * PW * PIX + 8 * i;
+    lmask[st] = cv ? ~0u : 0u;
+    hmask[st] = cv && 8 * i + 8 <= ROW ? ~0u : 0u;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int e = 8 * i + j;
+      const bool ok = cv && e < ROW;
+      const int ee = ok ? e : 0, kx = ee / PIX, cp = ee - kx * PIX;
+      const int rp = (cp >> 1) / C, c = (cp >> 1) - rp * C, q = rp + 2 * (cp & 1);
+      const int wi = ((ky * 3 + kx) * 4 * C + q * C + c) * a.Cout_pad + co_base;
+#pragma unroll
+      for (int t = 0; t < CT; ++t) af[st][t][j] = (elt_t)(ok ? Wt[wi + stem_ch(t, lx)] : 0.0f);
+    }
+  }
+  float bias[CT][4];
+#pragma unroll
+  for (int t = 0; t < CT; ++t)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) bias[t][r] = a.bias[co_base + stem_ch(t, 4 * kq + r)];
+  if (tid < 4) reinterpret_cast<uint32_t*>(patch + NELT)[tid] = 0u;
+  const int IH = 2 * a.H, IW = 2 * a.W;
+  const int ntx = (a.Wo + TW - 1) / TW, nty = (a.Ho + TH - 1) / TH;
+  const int ntiles = a.N * ntx * nty;
+  const int per = (ntiles + (int)gridDim.x - 1) / (int)gridDim.x;
+  const int t0 = ycx_xcd_remap(blockIdx.x, gridDim.x) * per, t1 = min(ntiles, t0 + per);
+  char* __restrict__ Y = reinterpret_cast<char*>(a.y);
+  for (int tl = t0; tl < t1; ++tl) {
+    const int ty = tl % nty, tr = tl / nty, tx = tr % ntx, n = tr / ntx;
+    const int oy0 = ty * TH, ox0 = tx * TW;
+    const int ry0 = oy0 * S - 1, rx0 = ox0 * S - 1;  // patch origin in the reorganised map
+    const float* Xn = X + (size_t)n * C * IH * IW;
+    __syncthreads();  // the previous tile's fragment reads are done
+    // (0) image rows 2 ry + rp, column pairs (2 rx, 2 rx + 1): item = ((lr, rp), c, lc), lc fastest
+    constexpr int ITEMS = PR * 2 * C * PW, NB = 8;
+    for (int i0 = tid; i0 < ITEMS; i0 += 256 * NB) {
+      float2 v[NB];
+#pragma unroll
+      for (int u = 0; u < NB; ++u) {
+        const int i = i0 + 256 * u;
+        const int lc = i % PW, r2 = i / PW, c = r2 % C, r3 = r2 / C, rp = r3 & 1, lr = r3 >> 1;
+        const int ry = ry0 + lr, rx = rx0 + lc;
+        const bool ok = i < ITEMS && (unsigned)ry < (unsigned)a.H && (unsigned)rx < (unsigned)a.W;
+        v[u] = ok ? *reinterpret_cast<const float2*>(Xn + ((size_t)c * IH + 2 * ry + rp) * IW + 2 * rx)
+                  : make_float2(0.0f, 0.0f);
+      }
+#pragma unroll
+      for (int u = 0; u < NB; ++u) {
+        const int i = i0 + 256 * u;
+        const int lc = i % PW, r2 = i / PW, c = r2 % C, r3 = r2 / C, rp = r3 & 1, lr = r3 >> 1;
+        if (i < ITEMS)
+          *reinterpret_cast<eltx2*>(patch + (lr * PW + lc) * PIX + (rp * C + c) * 2) =
+              eltx2{(elt_t)v[u].x, (elt_t)v[u].y};
+      }
+    }
+    __syncthreads();
+    // (1), (2): 16-pixel runs of the tile's rows, one wave each
+    constexpr int NG = TH * (TW / 16);
+    for (int g = wv; g < NG; g += 4) {
+      const int r = g / (TW / 16), cb = g - r * (TW / 16);
+      const int oy = oy0 + r, ox = ox0 + 16 * cb + lx;
+      if (oy >= a.Ho) break;                    // wave-uniform: rows below the map
+      if (ox0 + 16 * cb >= a.Wo) continue;      // wave-uniform: runs right of it
+      const elt_t* pb = patch + (r * S * PW + (16 * cb + lx) * S) * PIX;
+      eltx8 b[NSTEP];
+#pragma unroll
+      for (int st = 0; st < NSTEP; ++st) {
+        const uint2* p = reinterpret_cast<const uint2*>(pb + koff[st]);
+        const uint2 lo = p[0], hi = p[1];
+        b[st] = __builtin_bit_cast(eltx8, u32x4{lo.x & lmask[st], lo.y & lmask[st], hi.x & hmask[st],
+                                                hi.y & hmask[st]});
+      }
+      const size_t p0 = ((size_t)n * a.Ho + oy) * a.Wo + ox;
+#pragma unroll
+      for (int q = 0; q < CT / 2; ++q) {
+        f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int st = 0; st < NSTEP; ++st) {
+          c0 = YCX_MFMA16(af[st][2 * q], b[st], c0, 0, 0, 0);
+          c1 = YCX_MFMA16(af[st][2 * q + 1], b[st], c1, 0, 0, 0);
+        }
+        const int ch0 = co_base + 32 * q + 8 * kq;
+        if (ch0 < a.Cout && ox < a.Wo) {
+          float o[8];
+#pragma unroll
+          for (int rr = 0; rr < 4; ++rr) {
+            o[rr] = ycx_act<true>(c0[rr] + bias[2 * q][rr], a.act, a.slope);
+            o[4 + rr] = ycx_act<true>(c1[rr] + bias[2 * q + 1][rr], a.act, a.slope);
+          }
+          if constexpr (F8) {
+            const float sc = a.out_scale;
+            const uint32_t lo8 = f8x4_pack(o[0] * sc, o[1] * sc, o[2] * sc, o[3] * sc);
+            const uint32_t hi8 = f8x4_pack(o[4] * sc, o[5] * sc, o[6] * sc, o[7] * sc);
+            char* yo = Y + p0 * a.out_cs + a.out_coff + ch0;
+            if (YCX_OUT_OK(a, yo, sizeof(uint2))) *reinterpret_cast<uint2*>(yo) = make_uint2(lo8, hi8);
+          } else {
+            eltx8 ob;
+#pragma unroll
+            for (int rr = 0; rr < 8; ++rr) ob[rr] = (elt_t)o[rr];
+            char* yo = Y + (p0 * a.out_cs + a.out_coff + ch0) * 2;
+            if (YCX_OUT_OK(a, yo, sizeof(eltx8))) *reinterpret_cast<eltx8*>(yo) = ob;
+          }
+        }
+      }
+    }
+  }
+}
+
+// The fp32 parity form of the same conv: one thread per output pixel, 16 output channels at a
+// time; per tap the 4C values are gathered through the ReOrg index map and each channel's sum is
+// one fp32 FMA chain in the reference's K order (ky, kx, q * C + c) against the folded weights
+// broadcast from LDS (stem_kernel's scheme; the taps are re-read per channel group, from L1).
+template <int C>
+__global__ void __launch_bounds__(256) stem_reorg_f32(ConvArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float ws[];  // [9 * 4C][Cout_pad] + bias
+  constexpr int NT = 36 * C;
+  const float* Wt = reinterpret_cast<const float*>(a.w);
+  const int wn = NT * a.Cout_pad;
+  for (int i = threadIdx.x; i < wn; i += blockDim.x) ws[i] = Wt[i];
+  for (int i = threadIdx.x; i < a.Cout_pad; i += blockDim.x) ws[wn + i] = a.bias[i];
+  __syncthreads();
+  const int pr = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool pv = pr < a.M;  // tail threads compute a duplicate pixel and store nothing
+  const int p = pv ? pr : a.M - 1;
+  const int n = p / a.HoWo, rem = p - n * a.HoWo, oy = rem / a.Wo, ox = rem - oy * a.Wo;
+  const int IH = 2 * a.H, IW = 2 * a.W;
+  const float* Xn = reinterpret_cast<const float*>(a.x) + (size_t)n * C * IH * IW;
+  float* Yp = reinterpret_cast<float*>(a.y) + (size_t)p * a.out_cs + a.out_coff;
+  for (int c0 = 0; c0 < a.Cout; c0 += 16) {  // Cout_pad % 16 == 0: the weight rows cover c0 + 15
+    float v[16];
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = 0.0f;
+#pragma unroll 1
+    for (int tap = 0; tap < 9; ++tap) {
+      const int ky = tap / 3, kx = tap - 3 * ky;
+      const int ry = oy * a.S - 1 + ky, rx = ox * a.S - 1 + kx;
+      const bool ok = (unsigned)ry < (unsigned)a.H && (unsigned)rx < (unsigned)a.W;
+      float xv[4 * C];
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int c = 0; c < C; ++c)
+          xv[q * C + c] = ok ? Xn[((size_t)c * IH + 2 * ry + (q & 1)) * IW + 2 * rx + (q >> 1)] : 0.0f;
+#pragma unroll
+      for (int t = 0; t < 4 * C; ++t) {
+        const float* wr = ws + (tap * 4 * C + t) * a.Cout_pad + c0;
+#pragma unroll
+        for (int j4 = 0; j4 < 4; ++j4) {
+          const f32x4 w4 = *reinterpret_cast<const f32x4*>(wr + 4 * j4);
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[4 * j4 + j] = fmaf(xv[t], w4[j], v[4 * j4 + j]);
+        }
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < 16; ++j) v[j] = ycx_act<false>(v[j] + ws[wn + c0 + j], a.act, a.slope);
+    if (pv) {
+#pragma unroll
+      for (int j4 = 0; j4 < 4; ++j4)
+        if (c0 + 4 * j4 < a.Cout && YCX_OUT_OK(a, Yp + c0 + 4 * j4, sizeof(f32x4)))
+          *reinterpret_cast<f32x4*>(Yp + c0 + 4 * j4) = f32x4{v[4 * j4], v[4 * j4 + 1], v[4 * j4 + 2], v[4 * j4 + 3]};
+    }
+  }
+}
+
+// -------------------------------------------------------------------------
 // Stem + stride-2 conv, fused (yolov7's layers 0-1: 3x3 3->32, 3x3/s2 32->64).
 // Persistent 256-thread blocks (two per CU) walk a contiguous range of 4 x 32
 // tiles of the second conv's output, all its (<= 64) channels. Per block, once:
@@ -3943,6 +4165,8 @@ extern "C" ycx_status ycx_conv2d_pair_pool_f16(const ycx_conv_desc*, const ycx_c
                                                const float*, void*, const void*, const float*, void*, void*);
 extern "C" ycx_status ycx_stem_conv2_f16(const ycx_conv_desc*, const ycx_conv_desc*, const float*, const float*,
                                          const float*, const void*, const float*, void*, void*);
+extern "C" ycx_status ycx_stem_conv_reorg_f16(const ycx_conv_desc*, const float*, const float*, const float*, void*,
+                                              void*);
 #define YCX_TO_F16(cond, call) \
   do {                         \
     if (cond) return call;     \
@@ -4300,6 +4524,59 @@ extern "C" ycx_status YCX_SFX(ycx_stem_conv2)(const ycx_conv_desc* sd, const ycx
   YCX_STEM2(2, YCX_ACT_LEAKY, YCX_ACT_LEAKY)
   YCX_STEM2(2, YCX_ACT_NONE, YCX_ACT_NONE)
 #undef YCX_STEM2
+  return YCX_ERR_UNSUPPORTED;
+}
+
+extern "C" ycx_status YCX_SFX(ycx_stem_conv_reorg)(const ycx_conv_desc* d, const float* x, const float* w,
+                                                   const float* bias, void* y, void* stream) {
+  YCX_TO_F16(d && d->dtype == YCX_DT_F16, ycx_stem_conv_reorg_f16(d, x, w, bias, y, stream));
+  YCX_CHECK_ARG(d && x && w && bias && y);
+  YCX_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0 && d->cout > 0 && d->cout_pad >= d->cout);
+  YCX_CHECK_ARG(d->in_c_stride >= 1 && d->in_c_stride <= 4 && d->in_c_off == 0 && d->cin == 4 * d->in_c_stride);
+  YCX_CHECK_SUPPORTED(d->kh == 3 && d->kw == 3 && d->pad == 1 && (d->stride == 1 || d->stride == 2));
+  YCX_CHECK_ARG(d->ho == (d->h + 2 * d->pad - d->kh) / d->stride + 1);
+  YCX_CHECK_ARG(d->wo == (d->w + 2 * d->pad - d->kw) / d->stride + 1);
+  YCX_CHECK_SUPPORTED(d->cout % 8 == 0 && d->out_c_off >= 0 && d->out_c_off % 8 == 0 && d->out_c_stride % 8 == 0 &&
+                      d->out_c_off + d->cout <= d->out_c_stride);
+  YCX_CHECK_SUPPORTED(d->out_layout == YCX_OUT_NHWC && !d->in_pool);
+  YCX_CHECK_SUPPORTED(d->dtype == YCX_DT_ELT || d->dtype == YCX_DT_F32 || d->dtype == YCX_DT_FP8);
+  YCX_CHECK_SUPPORTED((long long)d->n * d->ho * d->wo < (1LL << 31) && (long long)d->h * d->w < (1LL << 28));
+  YCX_CHECK_SUPPORTED(d->act >= YCX_ACT_NONE && d->act <= YCX_ACT_SILU_PS &&
+                      (d->act != YCX_ACT_SILU_PS || d->dtype != YCX_DT_F32));
+  YCX_CHECK_SUPPORTED(reinterpret_cast<uintptr_t>(x) % 8 == 0);  // the image is read as column pairs
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  ConvArgs a = make_args(d, x, w, bias, y, nullptr);
+  a.Ktot = d->kh * d->kw * d->cin;  // fp32 weights: no fp8 row padding
+  const int C = d->in_c_stride;
+  if (d->dtype == YCX_DT_F32) {
+    YCX_CHECK_SUPPORTED(d->cout_pad % 16 == 0);
+    const size_t lds = ((size_t)a.Ktot * d->cout_pad + d->cout_pad) * sizeof(float);
+    YCX_CHECK_SUPPORTED(lds <= 64 * 1024);
+    const dim3 grid(ycx_cdiv(a.M, 256));
+#define YCX_REORG_F32(C_) \
+    if (C == C_) hipLaunchKernelGGL((stem_reorg_f32<C_>), grid, dim3(256), lds, st, a);
+    YCX_REORG_F32(1) YCX_REORG_F32(2) YCX_REORG_F32(3) YCX_REORG_F32(4)
+#undef YCX_REORG_F32
+    return ycx_launch_status();
+  }
+  YCX_CHECK_SUPPORTED(d->cout_pad == 32 || d->cout_pad % 64 == 0);
+  const bool f8 = d->dtype == YCX_DT_FP8;
+  const int th = 8 / d->stride, ct = d->cout_pad == 32 ? 2 : 4;
+  const long long ntiles = (long long)d->n * ((d->ho + th - 1) / th) * ((d->wo + kRoTW - 1) / kRoTW);
+  const dim3 g((unsigned)even_grid(ntiles, 768), (unsigned)(d->cout_pad / (16 * ct)));  // persistent: three blocks per CU
+#define YCX_REORG_CT(C_, S_, CT_)                                                          \
+  if (C == C_ && d->stride == S_ && ct == CT_) {                                           \
+    if (f8)                                                                                \
+      hipLaunchKernelGGL((stem_reorg_mfma<C_, S_, CT_, true>), g, dim3(256), 0, st, a);    \
+    else                                                                                   \
+      hipLaunchKernelGGL((stem_reorg_mfma<C_, S_, CT_>), g, dim3(256), 0, st, a);          \
+    return ycx_launch_status();                                                            \
+  }
+#define YCX_REORG(C_) \
+  YCX_REORG_CT(C_, 1, 2) YCX_REORG_CT(C_, 1, 4) YCX_REORG_CT(C_, 2, 2) YCX_REORG_CT(C_, 2, 4)
+  YCX_REORG(1) YCX_REORG(2) YCX_REORG(3) YCX_REORG(4)
+#undef YCX_REORG
+#undef YCX_REORG_CT
   return YCX_ERR_UNSUPPORTED;
 }
 

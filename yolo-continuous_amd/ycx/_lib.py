@@ -26,7 +26,7 @@ DT_BF16, DT_F32, DT_FP8, DT_F16 = 0, 1, 2, 3
 ACT_NONE, ACT_SILU, ACT_LEAKY, ACT_SILU_PS = 0, 1, 2, 3
 SILU_PS_K = -1.4426950408889634  # -log2(e): the pre-scale of YCX_ACT_SILU_PS weights and bias (ycx.h)
 OUT_NHWC, OUT_NCHW_F32, OUT_NHWC_UP2 = 0, 1, 2
-OP_CONV, OP_STEM, OP_POOL, OP_COPY, OP_STEM2, OP_HEAD, OP_CONV_PAIR = 1, 2, 3, 4, 5, 6, 7
+OP_CONV, OP_STEM, OP_POOL, OP_COPY, OP_STEM2, OP_HEAD, OP_CONV_PAIR, OP_STEM_REORG = 1, 2, 3, 4, 5, 6, 7, 8
 
 _i32 = ctypes.c_int32
 
@@ -137,6 +137,7 @@ _SIGS = [
     ("ycx_correct_boxes", _i32, [ctypes.POINTER(CorrectDesc), _VP, _VP, _VP, _VP]),
     ("ycx_stem_conv2", _i32, [ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _VP, _VP, _VP,
                               _VP]),
+    ("ycx_stem_conv_reorg", _i32, [ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _VP, _VP]),
     ("ycx_conv2d_pair", _i32, [ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _VP, _VP, _VP,
                                _VP, _VP]),
     ("ycx_conv2d_pair_pool", _i32, [ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc), ctypes.POINTER(ConvDesc),

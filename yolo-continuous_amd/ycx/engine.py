@@ -6,7 +6,8 @@ Lowering (once per input shape / device / precision):
    (nets/yolo.py:143-153: ``m.f`` indexing into the per-layer outputs) and lower
    each module into graph nodes — conv (BN folded, RepConv re-parameterised,
    Bottleneck residual fused into the epilogue), stem conv (first conv on the
-   fp32 NCHW image), max-pool, upsample, concat, Detect/IDetect heads.
+   fp32 NCHW image; ``stem_reorg`` when ReOrg precedes it: the space-to-depth is folded into
+   that conv's operand gather), max-pool, upsample, concat, Detect/IDetect heads.
 2. Passes: nearest-x2 upsample fused into its producing conv's store
    (YCX_OUT_NHWC_UP2); the SPPCSPC 5/9/13 pools run as a k5 cascade (exact for
    max with -inf padding); every concat input that a kernel produces is written
@@ -29,7 +30,7 @@ from torch import nn
 
 from . import _lib as L
 from .nets.common import (SP, SPP, SPPCSPC, SPPF, MP, Bottleneck, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC,
-                          Concat, Conv, RepConv)
+                          Concat, Conv, DownC, ReOrg, RepConv)
 from .nets.detect import Detect, IAuxDetect, IDetect
 
 
@@ -115,6 +116,9 @@ class Graph:
         self.nodes = []
 
     def add(self, kind, inputs, out, **p):
+        if kind != 'stem_reorg' and any(v.role == 'reorg' for v in inputs):
+            raise NotImplementedError("ycx: ReOrg is lowered only into the Conv (k3, p1, groups 1) that reads it; "
+                                      f"here a '{kind}' reads it")
         node = Node(kind, list(inputs), out, **p)
         out.producer = node
         for v in inputs:
@@ -130,9 +134,12 @@ class Graph:
         ho, wo = (x.h + 2 * p - k) // s + 1, (x.w + 2 * p - k) // s + 1
         out = Val(x.n, ho, wo, cout, role='output' if head else 'act')
         ins = [x] + ([residual] if residual is not None else [])
-        kind = 'stem' if x.role == 'input' else 'conv'
-        if kind == 'stem' and residual is not None:
+        kind = 'stem' if x.role == 'input' else 'stem_reorg' if x.role == 'reorg' else 'conv'
+        if kind != 'conv' and residual is not None:
             raise NotImplementedError("ycx: residual on the input conv")
+        if kind == 'stem_reorg' and not (k == 3 and p == 1 and s in (1, 2) and not head):
+            raise NotImplementedError("ycx: ReOrg is lowered only into a 3x3 / pad-1 Conv of stride 1 or 2 "
+                                      f"(ycx_stem_conv_reorg); got k{k} s{s} p{p}")
         return self.add(kind, ins, out, w=w64, b=b64, k=k, s=s, p=p, act=act[0], slope=act[1],
                         residual=residual, ho=ho, wo=wo, layout=L.OUT_NCHW_F32 if head else L.OUT_NHWC)
 
@@ -141,6 +148,17 @@ class Graph:
             raise NotImplementedError("ycx: pooling the raw input image")
         ho, wo = (x.h + 2 * p - k) // s + 1, (x.w + 2 * p - k) // s + 1
         return self.add('pool', [x], Val(x.n, ho, wo, x.c), k=k, s=s, p=p)
+
+    def reorg(self, x: Val):
+        """ReOrg (nets/common.py:43-51) of the model input: no node and no buffer, only the
+        (n, h/2, w/2, 4c) view that the one Conv reading it gathers through (``stem_reorg``)."""
+        if x.role != 'input':
+            raise NotImplementedError("ycx: ReOrg is lowered only on the model input (layer 0 of the P6 "
+                                      "configs); elsewhere it is out of scope for the HIP inference path")
+        if x.h % 2 or x.w % 2:
+            raise ValueError(f"ycx: ReOrg needs even image sides, got {x.h} x {x.w} (the reference's torch.cat "
+                             f"fails there)")
+        return Val(x.n, x.h // 2, x.w // 2, 4 * x.c, role='reorg')
 
     def upsample(self, x: Val):
         return self.add('up', [x], Val(x.n, 2 * x.h, 2 * x.w, x.c))
@@ -204,6 +222,11 @@ def lower_module(g: Graph, m, x):
         return g.conv(x, w, b, _square(m.kernel_size, 'k'), _square(m.stride, 's'), _square(m.padding, 'p'))
     if isinstance(m, (MP, SP)):
         return pool_module(g, m.m, x)
+    if isinstance(m, ReOrg):
+        return g.reorg(x)
+    if isinstance(m, DownC):  # nets/common.py:181-182
+        y1 = conv_module(g, m.cv2, conv_module(g, m.cv1, x))
+        return g.concat([y1, conv_module(g, m.cv3, pool_module(g, m.mp, x))])
     if isinstance(m, nn.MaxPool2d):
         return pool_module(g, m, x)
     if isinstance(m, Concat):
@@ -313,6 +336,10 @@ class Plan:
                 x = ys[m.f] if isinstance(m.f, int) else [x if j == -1 else ys[j] for j in m.f]
             x = lower_module(g, m, x)
             ys.append(x)
+        for v in ys:  # a ReOrg view feeds exactly one node, its stem_reorg conv (Graph.add refuses other kinds)
+            if isinstance(v, Val) and v.role == 'reorg' and (len(v.consumers) != 1 or x is v):
+                raise NotImplementedError("ycx: ReOrg is lowered only with one Conv (k3, p1, groups 1) as its "
+                                          f"only consumer; it has {len(v.consumers)} consumers")
         self.is_list = isinstance(x, list)
         self.out_vals = list(x) if self.is_list else [x]
         self.graph = g
@@ -323,7 +350,7 @@ class Plan:
     def conv_flops(self):
         """Algorithmic FLOPs: sum of 2*N*Ho*Wo*Cout*Cin*k*k over the folded convs."""
         return sum(2 * nd.inputs[0].n * nd.p['ho'] * nd.p['wo'] * int(nd.p['w'].shape[0]) * int(nd.p['w'].shape[1])
-                   * nd.p['k'] ** 2 for nd in self.graph.nodes if nd.kind in ('conv', 'stem'))
+                   * nd.p['k'] ** 2 for nd in self.graph.nodes if nd.kind in ('conv', 'stem', 'stem_reorg'))
 
     def counts(self):
         """Node kinds after the passes; 'conv' counts the original convs (a merged
@@ -383,7 +410,7 @@ class Plan:
             copies, off = [], 0
             for v in node.inputs:
                 if v.buf is None and v.role == 'act' and v.producer is not None and \
-                        v.producer.kind in ('conv', 'stem', 'pool', 'up'):
+                        v.producer.kind in ('conv', 'stem', 'stem_reorg', 'pool', 'up'):
                     v.buf, v.coff = out.buf, off
                 else:
                     copies.append((v, off))
@@ -685,7 +712,7 @@ class Engine:
         # size and the A/B switches, and a prepack file is reused at any batch size
         self.packed = {}
         self._conv_index = {id(nd): i for i, nd in enumerate(
-            nd for nd in self.graph.nodes if nd.kind in ('conv', 'stem'))}
+            nd for nd in self.graph.nodes if nd.kind in ('conv', 'stem', 'stem_reorg'))}
         pairs = self._stem2_pairs()
         fused = {id(c) for c in pairs.values()}
         for b in self.activation_bufs():  # the stem maps of fused stem2 pairs stay in LDS
@@ -711,7 +738,7 @@ class Engine:
                 ops.append(self._stem2_op(node, pairs[id(node)]))
             elif id(node) in chains:
                 ops.append(self._pair_op(node, chains[id(node)], *trios.get(id(node), ())))
-            elif k in ('conv', 'stem'):
+            elif k in ('conv', 'stem', 'stem_reorg'):
                 ops.append(self._conv_op(node, pool=pooled.get(id(node))))
             elif k == 'pool':
                 ops.append(self._pool_op(node, levels=len(cascades.get(id(node), [node]))))
@@ -738,7 +765,7 @@ class Engine:
         self._static_bound = False
 
     def _val_ptr(self, v, op_index, field):
-        if v.role == 'input':
+        if v.role in ('input', 'reorg'):  # a ReOrg view is read straight from the image
             self.input_slots.append((op_index, field))
             return None
         if v.role == 'output':
@@ -754,7 +781,7 @@ class Engine:
         p, x, out = node.p, node.inputs[0], node.out
         w64, b64 = p['w'], p['b']
         cout, cin, k = int(w64.shape[0]), int(w64.shape[1]), p['k']
-        stem = node.kind == 'stem'
+        stem = node.kind in ('stem', 'stem_reorg')
         cpad = self._cout_pad(cout, stem or bf16_weights)
         f8 = self.dt == L.DT_FP8
         if stem:  # [kh][kw][cin][cout_pad] fp32
@@ -802,6 +829,8 @@ class Engine:
         d.n, d.h, d.w, d.cin = x.n, x.h, x.w, cin
         if x.role == 'input':
             d.in_c_off, d.in_c_stride = 0, x.c
+        elif x.role == 'reorg':  # the image's own channel count; d.h, d.w, d.cin describe the reorganised map
+            d.in_c_off, d.in_c_stride = 0, x.c // 4
         else:
             d.in_c_off, d.in_c_stride = x.coff, x.buf.c
         if pool is not None:  # read the pool's (2h, 2w) input map instead of its output
@@ -827,10 +856,10 @@ class Engine:
 
     def _conv_op(self, node, pool=None):
         x, out, r = node.inputs[0], node.out, node.p['residual']
-        stem = node.kind == 'stem'
+        stem = node.kind in ('stem', 'stem_reorg')
         d, wt, bt, flops, shape = self._conv_parts(node, pool=pool)
         op = L.Op()
-        op.kind = L.OP_STEM if stem else L.OP_CONV
+        op.kind = L.OP_STEM_REORG if node.kind == 'stem_reorg' else L.OP_STEM if stem else L.OP_CONV
         op.d.conv = d
         idx = len(self.op_info)
         op.in_ = self._val_ptr(x if pool is None else pool.inputs[0], idx, 'in_')
@@ -846,7 +875,7 @@ class Engine:
                     if (t not in (24, 25) or d.cout_pad % 256 == 0) and (pool is None or t in (16, 18)):
                         tile = d.tile = t
                         break
-        name = 'stem' if stem else L.lib.ycx_conv_tile_name(tile).decode()
+        name = node.kind if stem else L.lib.ycx_conv_tile_name(tile).decode()
         if tile == 16 and d.stride == 2 and d.kh == 3 and d.kw == 3 and d.cin == 128 and pool is None:
             name += '+kcm'  # its own template instance (launch_glds: chunk-major K order), a row of its own in rocprof
         if not stem and pool is None and not _NO_KSPLIT:
@@ -866,7 +895,7 @@ class Engine:
 
     def _conv_bytes(self, d, wt, stem=False, pooled=False, residual=False, out_bytes=True):
         """Algorithmic HBM bytes of one conv launch: its input map read once (the
-        fp32 NCHW image for a stem; the 2x2-larger source map when an MP pool is
+        fp32 NCHW image for a stem -- a stem_reorg's 4C x h x w is the same C x 2h x 2w image --; the 2x2-larger source map when an MP pool is
         fused in), the packed weights once, the residual once, the output written
         once (4x for the fused x2 upsample; fp32 for NCHW heads). The per-op
         roofline in bench.py prices each op against max(FLOP / MFMA peak, these
@@ -1149,7 +1178,7 @@ class Engine:
             if v:
                 setattr(o, field, v + i0 * per_image)
 
-        if o.kind in (L.OP_CONV, L.OP_STEM, L.OP_STEM2):
+        if o.kind in (L.OP_CONV, L.OP_STEM, L.OP_STEM2, L.OP_STEM_REORG):
             d = o.d.pair[1] if o.kind == L.OP_STEM2 else o.d.conv
             first = o.d.pair[0] if o.kind == L.OP_STEM2 else d
             if o.kind == L.OP_CONV:
@@ -1182,7 +1211,7 @@ class Engine:
 
     @staticmethod
     def _op_out_h(op):
-        if op.kind in (L.OP_CONV, L.OP_STEM, L.OP_HEAD):
+        if op.kind in (L.OP_CONV, L.OP_STEM, L.OP_HEAD, L.OP_STEM_REORG):
             return op.d.conv.ho
         if op.kind == L.OP_STEM2:
             return op.d.pair[1].ho

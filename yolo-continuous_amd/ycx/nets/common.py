@@ -55,6 +55,12 @@ class SP(_Holder):
         self.m = nn.MaxPool2d(kernel_size=k, stride=s, padding=k // 2)
 
 
+class ReOrg(_Holder):
+    """Space-to-depth x(b, c, 2h, 2w) -> (b, 4c, h, w): cat of the (even, even), (odd, even),
+    (even, odd), (odd, odd) row / column samples (nets/common.py:43-51). No parameters; the
+    engine folds it into the operand gather of the Conv that reads it (ycx_stem_conv_reorg)."""
+
+
 class Concat(_Holder):
     """Channel concat (nets/common.py:54-60); never materialised on device."""
 
@@ -72,6 +78,18 @@ class Bottleneck(_Holder):
         self.cv1 = Conv(c1, c_, 1, 1)
         self.cv2 = Conv(c_, c2, 3, 1, g=g)
         self.add = shortcut and c1 == c2
+
+
+class DownC(_Holder):
+    """cat[cv2(cv1 x), cv3(maxpool_k x)]: the P6 down-sampling block (nets/common.py:171-182)."""
+
+    def __init__(self, c1, c2, n=1, k=2):
+        super().__init__()
+        c_ = int(c1)
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = Conv(c_, c2 // 2, 3, k)
+        self.cv3 = Conv(c1, c2 // 2, 1, 1)
+        self.mp = nn.MaxPool2d(kernel_size=k, stride=k)
 
 
 class SPP(_Holder):

@@ -26,7 +26,7 @@ from torch import nn
 
 from ..utils.helper_io import cvt_cfg
 from .common import (SP, SPP, SPPCSPC, SPPF, MP, Bottleneck, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC,
-                     Concat, Conv, ImplicitA, ImplicitM, RepConv)
+                     Concat, Conv, DownC, ImplicitA, ImplicitM, ReOrg, RepConv)
 from .detect import Detect, IAuxDetect, IDetect
 
 
@@ -40,19 +40,20 @@ _MODULES = {
     'BottleneckCSPC': BottleneckCSPC, 'SPP': SPP, 'SPPF': SPPF, 'ImplicitA': ImplicitA,
     'ImplicitM': ImplicitM, 'Detect': Detect, 'IDetect': IDetect, 'IAuxDetect': IAuxDetect,
     'nn.Conv2d': nn.Conv2d, 'nn.BatchNorm2d': nn.BatchNorm2d, 'nn.Upsample': nn.Upsample,
+    'ReOrg': ReOrg, 'DownC': DownC,
 }
 # Reference modules constructible by its parse_model but used by neither shipped
 # YAML: named here so the error says "out of scope", not "unknown".
 _OUT_OF_SCOPE = {
-    'ReOrg', 'Chuncat', 'Shortcut', 'Foldcut', 'RobustConv', 'RobustConv2', 'GhostConv', 'Stem', 'DownC',
+    'Chuncat', 'Shortcut', 'Foldcut', 'RobustConv', 'RobustConv2', 'GhostConv', 'Stem',
     'Res', 'ResX', 'Ghost', 'GhostSPPCSPC', 'GhostStem', 'dw_conv', 'Focus', 'Contract', 'Expand', 'Classify',
     'TransformerLayer', 'TransformerBlock', 'IBin', 'RepBottleneck',
 } | {f'{p}{s}' for p in ('Res', 'ResX', 'RepRes', 'RepResX', 'Ghost', 'RepBottleneck')
      for s in ('CSPA', 'CSPB', 'CSPC')}
 
-_CONV_LIKE = (nn.Conv2d, Conv, RepConv, SPP, SPPF, SPPCSPC, Bottleneck, BottleneckCSPA, BottleneckCSPB,
+_CONV_LIKE = (nn.Conv2d, Conv, RepConv, DownC, SPP, SPPF, SPPCSPC, Bottleneck, BottleneckCSPA, BottleneckCSPB,
               BottleneckCSPC)
-_CSP_LIKE = (SPPCSPC, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC)
+_CSP_LIKE = (DownC, SPPCSPC, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC)
 _ACTS = {'LeakyReLU': nn.LeakyReLU, 'SiLU': nn.SiLU, 'Identity': nn.Identity}
 _CALL_RE = re.compile(r'^(?:nn\.)?(\w+)\((.*)\)$')
 
@@ -114,6 +115,8 @@ def parse_model(d, ch, anchors, num_classes):
             args.append([ch[x] for x in f])
             if isinstance(args[1], int):
                 args[1] = [list(range(args[1] * 2))] * len(f)
+        elif m is ReOrg:
+            c2 = ch[f] * 4
         else:
             c2 = ch[f]
         m_ = nn.Sequential(*[m(*args) for _ in range(n)]) if n > 1 else m(*args)
