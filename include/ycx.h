@@ -13,6 +13,8 @@
  *                       RepConv.forward (re-parameterised)      nets/common.py:477-495
  *                       Detect head 1x1 convs (bias, no act)    nets/detect.py:27-38
  *                       IDetect conv + ImplicitA/M (folded)     nets/idetect.py:26-31
+ *   ycx_conv2d_grouped  Conv with g > 1 (small groups, depthwise) nets/common.py:97-109
+ *                       dw_conv                                 nets/common.py:20-22
  *   ycx_stem_conv       first Conv on the fp32 NCHW image       nets/common.py:105-106 (Cin=3)
  *   ycx_stem_conv2      first two Convs fused (3->32, then 3x3   cfg/net/yolov7.yaml:7-8,
  *                       stride 2 -> 64); the stem output stays   nets/common.py:97-109
@@ -43,6 +45,11 @@
 extern "C" {
 #endif
 
+/* The version stays 9 across the `groups` field appended to ycx_conv_desc (and the
+ * ycx_conv2d_grouped / YCX_OP_GCONV additions): the library and its ctypes mirror
+ * (ycx/_lib.py) are always built together in-tree and check each other's struct sizes
+ * (ycx_struct_size, ids 0 to 11 unchanged) at load time; a zero-initialised descriptor
+ * means what it meant before. */
 #define YCX_ABI_VERSION 9
 
 typedef int32_t ycx_status;
@@ -77,7 +84,7 @@ enum {
 };
 
 /* Convolution: NHWC activations, weights packed [cout_pad][kh][kw][cin] in the
- * activation dtype, fp32 bias[cout_pad] (BN folded in). groups = 1.
+ * activation dtype, fp32 bias[cout_pad] (BN folded in). groups = 1 (field `groups` 0 or 1).
  * YCX_DT_FP8: weight rows are zero-padded to a multiple of 128 bytes
  * ([cout_pad][ceil(kh*kw*cin / 128) * 128] e4m3 of w * s_w[co]); bias points
  * to fp32 [2 * cout_pad]: the bias, then dq[co] = 1 / (s_w[co] * s_x); the
@@ -106,6 +113,8 @@ typedef struct ycx_conv_desc {
                              * workspace (ycx_conv2d_ws, ycx_conv_workspace_size) and are summed in a
                              * fixed order by a second launch (bias, act, residual, store): deterministic.
                              * 16-bit LDS-DMA tiles only (16, 18, 56), r06. 0 or 1: no split */
+  int32_t groups;           /* 0 or 1: dense. > 1: only ycx_conv2d_grouped takes it (below); every other
+                             * entry point returns YCX_ERR_UNSUPPORTED */
 } ycx_conv_desc;
 
 /* Max-pool, NHWC, pad value -inf (torch.nn.MaxPool2d semantics, floor mode).
@@ -214,7 +223,8 @@ typedef struct ycx_head_desc {
 /* A pre-built op for ycx_run_ops (the static execution plan of Model.forward). */
 enum { YCX_OP_CONV = 1, YCX_OP_STEM = 2, YCX_OP_POOL = 3, YCX_OP_COPY = 4, YCX_OP_STEM2 = 5, YCX_OP_HEAD = 6,
        YCX_OP_CONV_PAIR = 7,
-       YCX_OP_STEM_REORG = 8 /* ycx_stem_conv_reorg: d.conv, in, weight, bias, out */ };
+       YCX_OP_STEM_REORG = 8 /* ycx_stem_conv_reorg: d.conv, in, weight, bias, out */,
+       YCX_OP_GCONV = 9 /* ycx_conv2d_grouped: d.conv, in, weight (fp32), bias, out, residual */ };
 typedef struct ycx_op {
   int32_t kind;
   int32_t pad_;
@@ -269,6 +279,20 @@ int32_t ycx_conv_tile_of(int32_t bid, int32_t nwg, int32_t n_ct, int32_t gc);
 
 ycx_status ycx_conv2d(const ycx_conv_desc* d, const void* x, const void* w,
                       const float* bias, void* y, const void* residual, void* stream);
+/* Grouped convolution, d->groups > 1 (Conv with g > 1, nets/common.py:97-109; dw_conv, :20-22):
+ * direct NHWC conv, VALU FMA with fp32 accumulation in a fixed order (kernel row, kernel column,
+ * input channel of the group), for the small groups the MFMA tiles cannot take:
+ *   cin_g = cin / groups == cout_g = cout / groups, cin_g in {1, 2, 4, 8, 16} (1: depthwise);
+ *   kh == kw in {3, 5, 7}, stride 1 or 2, pad == kh / 2; dtype bf16 / fp16 / f32.
+ * x, y, residual: NHWC channel slices as ycx_conv2d (in_c_*, out_c_*, res_c_*; offsets, strides and
+ * cout multiples of 8: a lane owns a 16-byte vector of 16-bit channels); cout_pad and tile are not used.
+ * w: fp32 in every dtype, [kh][kw][cout][cin_g], unscaled; bias: fp32 [cout].
+ * y = act(acc + bias) (+ residual), act YCX_ACT_NONE / SILU / LEAKY; 16-bit stores round to nearest
+ * even. Only YCX_OUT_NHWC, no in_pool, no k_split, no YCX_ACT_SILU_PS, no fp8: YCX_ERR_UNSUPPORTED,
+ * as is any other shape. Null pointers and inconsistent shapes (ho / wo, a slice past its stride,
+ * cin % groups != 0): YCX_ERR_BAD_ARG before any device call. */
+ycx_status ycx_conv2d_grouped(const ycx_conv_desc* d, const void* x, const float* w, const float* bias,
+                              void* y, const void* residual, void* stream);
 /* ycx_conv2d with a caller-owned workspace for d->k_split > 1 (split-K: fp32 partials of
  * every K range, then one reduce launch; ycx_conv2d itself returns YCX_ERR_CAPACITY for
  * k_split > 1). ycx_conv_workspace_size: the bytes it needs (0 without a split). */

@@ -4218,6 +4218,7 @@ extern "C" ycx_status YCX_SFX(ycx_conv2d_ws)(const ycx_conv_desc* d, const void*
   YCX_TO_F16(d && d->dtype == YCX_DT_F16,
              ycx_conv2d_ws_f16(d, x, w, bias, y, residual, workspace, workspace_bytes, stream));
   YCX_CHECK_ARG(d && x && w && bias && y);
+  YCX_CHECK_DENSE(d);
   YCX_CHECK_ARG(d->k_split >= 0);
   YCX_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0 && d->cin > 0 && d->cout > 0 && d->ho > 0 && d->wo > 0);
   YCX_CHECK_ARG(d->kh > 0 && d->kw > 0 && d->stride > 0 && d->pad >= 0);
@@ -4322,6 +4323,7 @@ extern "C" ycx_status YCX_SFX(ycx_conv2d_head)(const ycx_conv_desc* d, const ycx
   YCX_TO_F16(d && d->dtype == YCX_DT_F16,
              ycx_conv2d_head_f16(d, h, x, w, bias, heads, cand, cand_rows, cand_counts, status, stream));
   YCX_CHECK_ARG(d && h && x && w && bias && cand && cand_rows && cand_counts);
+  YCX_CHECK_DENSE(d);
   YCX_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0 && d->cin > 0 && d->cout > 0 && d->ho == d->h && d->wo == d->w);
   YCX_CHECK_ARG(d->in_c_off >= 0 && d->in_c_off + d->cin <= d->in_c_stride && d->cout_pad >= d->cout);
   YCX_CHECK_ARG(h->na > 0 && h->na <= 8 && h->nc > 0 && h->no == h->nc + 5 && h->na * h->no == d->cout);
@@ -4347,6 +4349,8 @@ extern "C" ycx_status YCX_SFX(ycx_conv2d_pair)(const ycx_conv_desc* da, const yc
   YCX_TO_F16(da && da->dtype == YCX_DT_F16,
              ycx_conv2d_pair_f16(da, db, x, wa, ba, ya, wb, bb, yb, stream));
   YCX_CHECK_ARG(da && db && x && wa && ba && wb && bb && yb);
+  YCX_CHECK_DENSE(da);
+  YCX_CHECK_DENSE(db);
   YCX_CHECK_ARG(da->n > 0 && da->h > 0 && da->w > 0 && da->cin > 0 && da->cout > 0);
   YCX_CHECK_ARG(da->ho == da->h && da->wo == da->w && db->n == da->n && db->h == da->ho && db->w == da->wo &&
                 db->ho == db->h && db->wo == db->w && db->cin == da->cout && db->cout > 0);
@@ -4376,6 +4380,9 @@ extern "C" ycx_status YCX_SFX(ycx_conv2d_pair_pool)(const ycx_conv_desc* da, con
   YCX_TO_F16(da && da->dtype == YCX_DT_F16,
              ycx_conv2d_pair_pool_f16(da, db, dc, x, wa, ba, ya, wb, bb, yb, wc, bc, yc, stream));
   YCX_CHECK_ARG(da && db && dc && x && wa && ba && wb && bb && yb && wc && bc && yc);
+  YCX_CHECK_DENSE(da);
+  YCX_CHECK_DENSE(db);
+  YCX_CHECK_DENSE(dc);
   YCX_CHECK_ARG(da->n > 0 && da->h > 0 && da->w > 0 && da->cin > 0 && da->cout > 0);
   YCX_CHECK_ARG(da->ho == da->h && da->wo == da->w && db->n == da->n && db->h == da->ho && db->w == da->wo &&
                 db->ho == db->h && db->wo == db->w && db->cin == da->cout && db->cout > 0);
@@ -4410,6 +4417,7 @@ extern "C" ycx_status YCX_SFX(ycx_stem_conv)(const ycx_conv_desc* d, const float
                                              const float* bias, void* y, void* stream) {
   YCX_TO_F16(d && d->dtype == YCX_DT_F16, ycx_stem_conv_f16(d, x, w, bias, y, stream));
   YCX_CHECK_ARG(d && x && w && bias && y);
+  YCX_CHECK_DENSE(d);
   YCX_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0 && d->cout > 0 && d->cout_pad >= d->cout);
   YCX_CHECK_ARG(d->ho == (d->h + 2 * d->pad - d->kh) / d->stride + 1);
   YCX_CHECK_ARG(d->wo == (d->w + 2 * d->pad - d->kw) / d->stride + 1);
@@ -4475,6 +4483,8 @@ extern "C" ycx_status YCX_SFX(ycx_stem_conv2)(const ycx_conv_desc* sd, const ycx
   YCX_TO_F16(cd && cd->dtype == YCX_DT_F16,
              ycx_stem_conv2_f16(sd, cd, x, w_stem, b_stem, w_conv, b_conv, y, stream));
   YCX_CHECK_ARG(sd && cd && x && w_stem && b_stem && w_conv && b_conv && y);
+  YCX_CHECK_DENSE(sd);
+  YCX_CHECK_DENSE(cd);
   YCX_CHECK_ARG(sd->n > 0 && sd->h > 0 && sd->w > 0 && cd->n == sd->n);
   YCX_CHECK_ARG(sd->ho == (sd->h + 2 * sd->pad - sd->kh) / sd->stride + 1);
   YCX_CHECK_ARG(sd->wo == (sd->w + 2 * sd->pad - sd->kw) / sd->stride + 1);
@@ -4531,6 +4541,7 @@ extern "C" ycx_status YCX_SFX(ycx_stem_conv_reorg)(const ycx_conv_desc* d, const
                                                    const float* bias, void* y, void* stream) {
   YCX_TO_F16(d && d->dtype == YCX_DT_F16, ycx_stem_conv_reorg_f16(d, x, w, bias, y, stream));
   YCX_CHECK_ARG(d && x && w && bias && y);
+  YCX_CHECK_DENSE(d);
   YCX_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0 && d->cout > 0 && d->cout_pad >= d->cout);
   YCX_CHECK_ARG(d->in_c_stride >= 1 && d->in_c_stride <= 4 && d->in_c_off == 0 && d->cin == 4 * d->in_c_stride);
   YCX_CHECK_SUPPORTED(d->kh == 3 && d->kw == 3 && d->pad == 1 && (d->stride == 1 || d->stride == 2));

@@ -17,6 +17,9 @@ typedef __attribute__((ext_vector_type(4))) float f32x4;
     if (!(cond)) return YCX_ERR_UNSUPPORTED; \
   } while (0)
 
+// The dense conv entry points take groups 0 / 1 only (grouped: ycx_conv2d_grouped, ycx_gconv.hip).
+#define YCX_CHECK_DENSE(d) YCX_CHECK_SUPPORTED((d)->groups <= 1)
+
 static inline ycx_status ycx_launch_status() {
   hipError_t e = hipGetLastError();
   return e == hipSuccess ? YCX_OK : YCX_ERR_LAUNCH;

@@ -27,6 +27,7 @@ ACT_NONE, ACT_SILU, ACT_LEAKY, ACT_SILU_PS = 0, 1, 2, 3
 SILU_PS_K = -1.4426950408889634  # -log2(e): the pre-scale of YCX_ACT_SILU_PS weights and bias (ycx.h)
 OUT_NHWC, OUT_NCHW_F32, OUT_NHWC_UP2 = 0, 1, 2
 OP_CONV, OP_STEM, OP_POOL, OP_COPY, OP_STEM2, OP_HEAD, OP_CONV_PAIR, OP_STEM_REORG = 1, 2, 3, 4, 5, 6, 7, 8
+OP_GCONV = 9
 
 _i32 = ctypes.c_int32
 
@@ -37,7 +38,7 @@ class ConvDesc(ctypes.Structure):
         "ho", "wo", "cout", "cout_pad", "out_c_off", "out_c_stride",
         "kh", "kw", "stride", "pad", "act")] + [("leaky_slope", ctypes.c_float)] + [
         (n, _i32) for n in ("dtype", "out_layout", "res_c_off", "res_c_stride", "tile")] + [
-        ("out_scale", ctypes.c_float), ("res_scale", ctypes.c_float), ("in_pool", _i32), ("k_split", _i32)]
+        ("out_scale", ctypes.c_float), ("res_scale", ctypes.c_float), ("in_pool", _i32), ("k_split", _i32), ("groups", _i32)]
 
 
 class PoolDesc(ctypes.Structure):
@@ -125,6 +126,7 @@ _SIGS = [
     ("ycx_conv_pick_tile", _i32, [ctypes.POINTER(ConvDesc)]),
     ("ycx_conv_tile_of", _i32, [_i32, _i32, _i32, _i32]),
     ("ycx_conv2d", _i32, [ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _VP, _VP, _VP]),
+    ("ycx_conv2d_grouped", _i32, [ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _VP, _VP, _VP]),
     ("ycx_conv_workspace_size", ctypes.c_size_t, [ctypes.POINTER(ConvDesc)]),
     ("ycx_conv2d_ws", _i32, [ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _VP, _VP, _VP, ctypes.c_size_t, _VP]),
     ("ycx_conv_pick_ksplit", _i32, [ctypes.POINTER(ConvDesc)]),

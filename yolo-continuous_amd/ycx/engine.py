@@ -30,7 +30,7 @@ from torch import nn
 
 from . import _lib as L
 from .nets.common import (SP, SPP, SPPCSPC, SPPF, MP, Bottleneck, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC,
-                          Concat, Conv, DownC, ReOrg, RepConv)
+                          Concat, Conv, DownC, ReOrg, RepConv, Res, RobustConv)
 from .nets.detect import Detect, IAuxDetect, IDetect
 
 
@@ -111,6 +111,11 @@ def act_of(mod):
     raise NotImplementedError(f"ycx: activation {type(mod).__name__} has no HIP epilogue")
 
 
+# what ycx_conv2d_grouped takes (include/ycx.h): channels per group (cin_g == cout_g) and kernel sizes
+GCONV_CIN_G = (1, 2, 4, 8, 16)
+GCONV_K = (3, 5, 7)
+
+
 class Graph:
     def __init__(self):
         self.nodes = []
@@ -127,8 +132,10 @@ class Graph:
         return out
 
     # ---- primitive ops ----
-    def conv(self, x: Val, w64, b64, k, s, p, act=(L.ACT_NONE, 0.0), residual=None, head=False):
+    def conv(self, x: Val, w64, b64, k, s, p, act=(L.ACT_NONE, 0.0), residual=None, head=False, groups=1):
         cout, cin = int(w64.shape[0]), int(w64.shape[1])
+        if groups > 1:
+            return self._gconv(x, w64, b64, k, s, p, act, residual, head, groups)
         if cin != x.c:
             raise NotImplementedError(f"ycx: grouped/mismatched conv (cin {cin} vs input {x.c})")
         ho, wo = (x.h + 2 * p - k) // s + 1, (x.w + 2 * p - k) // s + 1
@@ -142,6 +149,27 @@ class Graph:
                                       f"(ycx_stem_conv_reorg); got k{k} s{s} p{p}")
         return self.add(kind, ins, out, w=w64, b=b64, k=k, s=s, p=p, act=act[0], slope=act[1],
                         residual=residual, ho=ho, wo=wo, layout=L.OUT_NCHW_F32 if head else L.OUT_NHWC)
+
+    def _gconv(self, x, w64, b64, k, s, p, act, residual, head, groups):
+        """A grouped conv (weights [cout][cin_g][k][k]) as a node of its own kind, 'gconv'
+        (ycx_conv2d_grouped): every pass that fuses, merges, pairs or splits convs looks for
+        kind 'conv' and so leaves it alone; only the concat-slice aliasing takes it."""
+        cout, cin_g = int(w64.shape[0]), int(w64.shape[1])
+        if x.role in ('input', 'reorg'):
+            raise NotImplementedError("ycx: grouped conv on the model input")
+        if cin_g * groups != x.c or cout % groups:
+            raise NotImplementedError(f"ycx: grouped/mismatched conv (cin {cin_g} x {groups} groups vs input {x.c})")
+        cout_g = cout // groups
+        if not (cin_g == cout_g and cin_g in GCONV_CIN_G and k in GCONV_K and p == k // 2 and s in (1, 2)
+                and cout % 8 == 0 and not head):
+            raise NotImplementedError(
+                f"ycx: grouped conv with cin_g {cin_g}, cout_g {cout_g}, k {k} (s {s}, p {p}, cout {cout}) has no HIP "
+                f"kernel: ycx_conv2d_grouped takes cin_g == cout_g in {GCONV_CIN_G}, k in {GCONV_K}, p == k // 2, "
+                f"s 1 or 2, cout % 8 == 0")
+        ho, wo = (x.h + 2 * p - k) // s + 1, (x.w + 2 * p - k) // s + 1
+        ins = [x] + ([residual] if residual is not None else [])
+        return self.add('gconv', ins, Val(x.n, ho, wo, cout), w=w64, b=b64, k=k, s=s, p=p, act=act[0], slope=act[1],
+                        residual=residual, ho=ho, wo=wo, layout=L.OUT_NHWC, groups=groups)
 
     def pool(self, x: Val, k, s, p):
         if x.role == 'input':
@@ -172,11 +200,30 @@ class Graph:
 
 def conv_module(g: Graph, m: Conv, x: Val, residual=None):
     c = m.conv
-    if c.groups != 1 or _pair(c.dilation) != (1, 1):
-        raise NotImplementedError("ycx: grouped/dilated conv")
+    if _pair(c.dilation) != (1, 1):
+        raise NotImplementedError("ycx: dilated conv")
     w, b = fold_bn(c.weight, m.bn)
     return g.conv(x, w, b, _square(c.kernel_size, 'kernel'), _square(c.stride, 'stride'),
-                  _square(c.padding, 'padding'), act_of(m.act), residual=residual)
+                  _square(c.padding, 'padding'), act_of(m.act), residual=residual, groups=int(c.groups))
+
+
+def fold_robustconv(m: RobustConv):
+    """RobustConv's biased 1x1 with its layer scale folded in, float64 (W, b):
+    (W x + b) * gamma = (gamma W) x + gamma b (nets/common.py:123-124)."""
+    c = m.conv1x1
+    w = c.weight.detach().to('cpu', torch.float64)
+    b = c.bias.detach().to('cpu', torch.float64)
+    if m.gamma is not None:
+        gm = m.gamma.detach().to('cpu', torch.float64)
+        w, b = w * gm.reshape(-1, 1, 1, 1), b * gm
+    return w, b
+
+
+def check_plan_precision(plan, precision):
+    """What a plan cannot run in a given precision, raised before anything is allocated."""
+    if precision == 'fp8' and any(nd.kind == 'gconv' for nd in plan.graph.nodes):
+        raise NotImplementedError("ycx: grouped conv has no fp8 path (ycx_conv2d_grouped takes bf16, fp16 and f32); "
+                                  "run this model in 'fp16', 'bf16' or 'f32'")
 
 
 def pool_module(g: Graph, mp: nn.MaxPool2d, x: Val):
@@ -217,9 +264,10 @@ def lower_module(g: Graph, m, x):
         w = m.weight.detach().to('cpu', torch.float64)
         b = m.bias.detach().to('cpu', torch.float64) if m.bias is not None else torch.zeros(w.shape[0],
                                                                                             dtype=torch.float64)
-        if m.groups != 1:
-            raise NotImplementedError("ycx: grouped conv")
-        return g.conv(x, w, b, _square(m.kernel_size, 'k'), _square(m.stride, 's'), _square(m.padding, 'p'))
+        if _pair(m.dilation) != (1, 1):
+            raise NotImplementedError("ycx: dilated conv")
+        return g.conv(x, w, b, _square(m.kernel_size, 'k'), _square(m.stride, 's'), _square(m.padding, 'p'),
+                      groups=int(m.groups))
     if isinstance(m, (MP, SP)):
         return pool_module(g, m.m, x)
     if isinstance(m, ReOrg):
@@ -244,6 +292,12 @@ def lower_module(g: Graph, m, x):
     if isinstance(m, Bottleneck):
         y = conv_module(g, m.cv1, x)
         return conv_module(g, m.cv2, y, residual=x if m.add else None)
+    if isinstance(m, Res):  # ResX too (nets/common.py:212-230); the shortcut is cv3's epilogue residual
+        y = conv_module(g, m.cv2, conv_module(g, m.cv1, x))
+        return conv_module(g, m.cv3, y, residual=x if m.add else None)
+    if isinstance(m, RobustConv):  # nets/common.py:121-124; its channels_last call changes no value
+        w, b = fold_robustconv(m)
+        return g.conv(conv_module(g, m.conv_dw, x), w, b, 1, 1, 0)
     if isinstance(m, SPPCSPC):
         x1 = conv_module(g, m.cv4, conv_module(g, m.cv3, conv_module(g, m.cv1, x)))
         y1 = conv_module(g, m.cv6, conv_module(g, m.cv5, g.concat([x1] + pyramid(g, x1, list(m.m)))))
@@ -258,6 +312,7 @@ def lower_module(g: Graph, m, x):
     if isinstance(m, SPP):
         x1 = conv_module(g, m.cv1, x)
         return conv_module(g, m.cv2, g.concat([x1] + pyramid(g, x1, list(m.m))))
+    # the CSP blocks: also their Res*CSP* / ResX*CSP* subclasses, whose m is a Sequential of Res
     if isinstance(m, BottleneckCSPA):
         y1 = lower_module(g, m.m, conv_module(g, m.cv1, x))
         return conv_module(g, m.cv3, g.concat([y1, conv_module(g, m.cv2, x)]))
@@ -348,9 +403,10 @@ class Plan:
 
     @property
     def conv_flops(self):
-        """Algorithmic FLOPs: sum of 2*N*Ho*Wo*Cout*Cin*k*k over the folded convs."""
+        """Algorithmic FLOPs: sum of 2*N*Ho*Wo*Cout*Cin*k*k over the folded convs (a grouped conv:
+        Cin = cin_g, the second dim of its weights)."""
         return sum(2 * nd.inputs[0].n * nd.p['ho'] * nd.p['wo'] * int(nd.p['w'].shape[0]) * int(nd.p['w'].shape[1])
-                   * nd.p['k'] ** 2 for nd in self.graph.nodes if nd.kind in ('conv', 'stem', 'stem_reorg'))
+                   * nd.p['k'] ** 2 for nd in self.graph.nodes if nd.kind in ('conv', 'stem', 'stem_reorg', 'gconv'))
 
     def counts(self):
         """Node kinds after the passes; 'conv' counts the original convs (a merged
@@ -410,7 +466,7 @@ class Plan:
             copies, off = [], 0
             for v in node.inputs:
                 if v.buf is None and v.role == 'act' and v.producer is not None and \
-                        v.producer.kind in ('conv', 'stem', 'stem_reorg', 'pool', 'up'):
+                        v.producer.kind in ('conv', 'stem', 'stem_reorg', 'gconv', 'pool', 'up'):
                     v.buf, v.coff = out.buf, off
                 else:
                     copies.append((v, off))
@@ -494,6 +550,7 @@ class Engine:
             raise RuntimeError("ycx: the HIP path needs the model input on a ROCm device (tensor.to('cuda')); "
                                "there is no CPU path")
         self.plan = Plan(model, shape)
+        check_plan_precision(self.plan, precision)
         self.shape, self.device, self.precision = self.plan.shape, device, precision
         self.dtype = {'bf16': torch.bfloat16, 'f32': torch.float32, 'fp8': torch.float8_e4m3fn,
                       'fp16': torch.float16}[precision]
@@ -712,7 +769,7 @@ class Engine:
         # size and the A/B switches, and a prepack file is reused at any batch size
         self.packed = {}
         self._conv_index = {id(nd): i for i, nd in enumerate(
-            nd for nd in self.graph.nodes if nd.kind in ('conv', 'stem', 'stem_reorg'))}
+            nd for nd in self.graph.nodes if nd.kind in ('conv', 'stem', 'stem_reorg', 'gconv'))}
         pairs = self._stem2_pairs()
         fused = {id(c) for c in pairs.values()}
         for b in self.activation_bufs():  # the stem maps of fused stem2 pairs stay in LDS
@@ -740,6 +797,8 @@ class Engine:
                 ops.append(self._pair_op(node, chains[id(node)], *trios.get(id(node), ())))
             elif k in ('conv', 'stem', 'stem_reorg'):
                 ops.append(self._conv_op(node, pool=pooled.get(id(node))))
+            elif k == 'gconv':
+                ops.append(self._gconv_op(node))
             elif k == 'pool':
                 ops.append(self._pool_op(node, levels=len(cascades.get(id(node), [node]))))
             elif k == 'up':  # an unfused upsample may write a slice of a concat buffer
@@ -891,6 +950,49 @@ class Engine:
         nbytes = self._conv_bytes(d, wt, **kw)
         self.op_info.append(dict(kind=node.kind, name=name, flops=flops, shape=shape, parts=node.p.get('parts', 1),
                                  bytes=nbytes, out_bytes=nbytes - self._conv_bytes(d, wt, out_bytes=False, **kw)))
+        return op
+
+    def _gconv_op(self, node):
+        """One OP_GCONV (ycx_conv2d_grouped): fp32 weights [kh][kw][cout][cin_g] and fp32 bias [cout] in every
+        precision, unscaled -- a SiLU gconv runs the plain YCX_ACT_SILU epilogue, never the pre-scaled one."""
+        p, x, out, r = node.p, node.inputs[0], node.out, node.p['residual']
+        w64, b64 = p['w'], p['b']
+        cout, cin_g, k = int(w64.shape[0]), int(w64.shape[1]), p['k']
+        wshape, bshape = (k, k, cout, cin_g), (cout,)
+        i = 2 * self._conv_index[id(node)]
+        if self.prepacked is not None:
+            wt, bt = self.prepacked.get(f"p{i}"), self.prepacked.get(f"p{i + 1}")
+            if wt is None or bt is None or tuple(wt.shape) != wshape or wt.dtype != torch.float32 or \
+                    tuple(bt.shape) != bshape or bt.dtype != torch.float32:
+                raise ValueError(f"ycx: prepacked weights do not match this plan at tensor p{i}")
+        else:
+            wt = w64.permute(2, 3, 0, 1).contiguous().to(torch.float32)
+            bt = b64.to(torch.float32)
+        wt, bt = wt.to(self.device), bt.to(self.device)
+        self.params += [wt, bt]
+        self.packed[f"p{i}"], self.packed[f"p{i + 1}"] = wt, bt
+        d = L.ConvDesc()
+        d.n, d.h, d.w, d.cin, d.in_c_off, d.in_c_stride = x.n, x.h, x.w, x.c, x.coff, x.buf.c
+        d.ho, d.wo, d.cout, d.cout_pad, d.out_c_off, d.out_c_stride = p['ho'], p['wo'], cout, cout, out.coff, out.buf.c
+        d.kh = d.kw = k
+        d.stride, d.pad, d.act, d.leaky_slope = p['s'], p['p'], p['act'], p['slope']
+        d.dtype, d.out_layout, d.groups = self.dt, L.OUT_NHWC, p['groups']
+        if r is not None:
+            d.res_c_off, d.res_c_stride = r.coff, r.buf.c
+        d.out_scale = d.res_scale = 1.0
+        flops = 2 * x.n * p['ho'] * p['wo'] * cout * cin_g * k * k
+        self.conv_flops += flops
+        op = L.Op()
+        op.kind = L.OP_GCONV
+        op.d.conv = d
+        op.in_ = x.buf.tensor.data_ptr()
+        op.weight, op.bias = wt.data_ptr(), bt.data_ptr()
+        op.out = out.buf.tensor.data_ptr()
+        op.residual = r.buf.tensor.data_ptr() if r is not None else None
+        nbytes = self._conv_bytes(d, wt, residual=r is not None)
+        self.op_info.append(dict(kind='gconv', name=f"gconv_g{cin_g}_k{k}s{p['s']}", flops=flops,
+                                 shape=(x.n, x.h, x.w, x.c, cout, k, p['s']), parts=1, bytes=nbytes,
+                                 out_bytes=nbytes - self._conv_bytes(d, wt, residual=r is not None, out_bytes=False)))
         return op
 
     def _conv_bytes(self, d, wt, stem=False, pooled=False, residual=False, out_bytes=True):
@@ -1178,10 +1280,10 @@ class Engine:
             if v:
                 setattr(o, field, v + i0 * per_image)
 
-        if o.kind in (L.OP_CONV, L.OP_STEM, L.OP_STEM2, L.OP_STEM_REORG):
+        if o.kind in (L.OP_CONV, L.OP_STEM, L.OP_STEM2, L.OP_STEM_REORG, L.OP_GCONV):
             d = o.d.pair[1] if o.kind == L.OP_STEM2 else o.d.conv
             first = o.d.pair[0] if o.kind == L.OP_STEM2 else d
-            if o.kind == L.OP_CONV:
+            if o.kind in (L.OP_CONV, L.OP_GCONV):
                 shift('in_', (4 if d.in_pool else 1) * d.h * d.w * d.in_c_stride * es)
             else:  # fp32 NCHW image
                 shift('in_', first.cin * first.h * first.w * 4)
@@ -1211,7 +1313,7 @@ class Engine:
 
     @staticmethod
     def _op_out_h(op):
-        if op.kind in (L.OP_CONV, L.OP_STEM, L.OP_HEAD, L.OP_STEM_REORG):
+        if op.kind in (L.OP_CONV, L.OP_STEM, L.OP_HEAD, L.OP_STEM_REORG, L.OP_GCONV):
             return op.d.conv.ho
         if op.kind == L.OP_STEM2:
             return op.d.pair[1].ho

@@ -11,6 +11,9 @@ Reference: nets/common.py (line numbers cited per class).
 """
 from __future__ import annotations
 
+import math
+
+import torch
 from torch import nn
 
 
@@ -37,6 +40,22 @@ class Conv(_Holder):
         self.conv = nn.Conv2d(c1, c2, k, s, autopad(k, p), groups=g, bias=False)
         self.bn = nn.BatchNorm2d(c2)
         self.act = nn.SiLU() if act is True else (act if isinstance(act, nn.Module) else nn.Identity())
+
+
+def dw_conv(c1, c2, k=1, s=1, act=True):
+    """Depthwise Conv: groups = gcd(c1, c2) (nets/common.py:20-22); a function there too."""
+    return Conv(c1, c2, k, s, g=math.gcd(c1, c2), act=act)
+
+
+class RobustConv(_Holder):
+    """conv1x1(conv_dw(x)) * gamma: a depthwise k x k Conv, a biased 1x1 conv and a learned
+    per-channel layer scale (nets/common.py:112-124). The engine folds gamma into the 1x1."""
+
+    def __init__(self, c1, c2, k=7, s=1, p=None, g=1, act=True, layer_scale_init_value=1e-6):
+        super().__init__()
+        self.conv_dw = Conv(c1, c1, k=k, s=s, p=p, g=c1, act=act)
+        self.conv1x1 = nn.Conv2d(c1, c2, 1, 1, 0, groups=1, bias=True)
+        self.gamma = nn.Parameter(layer_scale_init_value * torch.ones(c2)) if layer_scale_init_value > 0 else None
 
 
 class MP(_Holder):
@@ -78,6 +97,25 @@ class Bottleneck(_Holder):
         self.cv1 = Conv(c1, c_, 1, 1)
         self.cv2 = Conv(c_, c2, 3, 1, g=g)
         self.add = shortcut and c1 == c2
+
+
+class Res(_Holder):
+    """x + cv3(cv2(cv1(x))) when shortcut and c1 == c2, cv2 a (grouped) 3x3 (nets/common.py:212-223)."""
+
+    def __init__(self, c1, c2, shortcut=True, g=1, e=0.5):
+        super().__init__()
+        c_ = int(c2 * e)
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = Conv(c_, c_, 3, 1, g=g)
+        self.cv3 = Conv(c_, c2, 1, 1)
+        self.add = shortcut and c1 == c2
+
+
+class ResX(Res):
+    """Res with 32 groups (nets/common.py:226-230)."""
+
+    def __init__(self, c1, c2, shortcut=True, g=32, e=0.5):
+        super().__init__(c1, c2, shortcut, g, e)
 
 
 class DownC(_Holder):
@@ -154,6 +192,60 @@ class BottleneckCSPC(_Holder):
         self.cv3 = Conv(c_, c_, 1, 1)
         self.cv4 = Conv(2 * c_, c2, 1, 1)
         self.m = nn.Sequential(*[Bottleneck(c_, c_, shortcut, g, e=1.0) for _ in range(n)])
+
+
+class ResCSPA(BottleneckCSPA):
+    """BottleneckCSPA over Res blocks (nets/common.py:344-349)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*[Res(c_, c_, shortcut, g, e=0.5) for _ in range(n)])
+
+
+class ResCSPB(BottleneckCSPB):
+    """BottleneckCSPB over Res blocks (nets/common.py:352-357)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2)
+        self.m = nn.Sequential(*[Res(c_, c_, shortcut, g, e=0.5) for _ in range(n)])
+
+
+class ResCSPC(BottleneckCSPC):
+    """BottleneckCSPC over Res blocks (nets/common.py:360-365)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*[Res(c_, c_, shortcut, g, e=0.5) for _ in range(n)])
+
+
+class ResXCSPA(ResCSPA):
+    """ResCSPA with 32 groups and e = 1 inner blocks (nets/common.py:368-373)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=32, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*[Res(c_, c_, shortcut, g, e=1.0) for _ in range(n)])
+
+
+class ResXCSPB(ResCSPB):
+    """ResCSPB with 32 groups and e = 1 inner blocks (nets/common.py:376-381)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=32, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2)
+        self.m = nn.Sequential(*[Res(c_, c_, shortcut, g, e=1.0) for _ in range(n)])
+
+
+class ResXCSPC(ResCSPC):
+    """ResCSPC with 32 groups and e = 1 inner blocks (nets/common.py:384-389)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=32, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*[Res(c_, c_, shortcut, g, e=1.0) for _ in range(n)])
 
 
 class ImplicitA(_Holder):

@@ -26,7 +26,8 @@ from torch import nn
 
 from ..utils.helper_io import cvt_cfg
 from .common import (SP, SPP, SPPCSPC, SPPF, MP, Bottleneck, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC,
-                     Concat, Conv, DownC, ImplicitA, ImplicitM, ReOrg, RepConv)
+                     Concat, Conv, DownC, ImplicitA, ImplicitM, ReOrg, RepConv, Res, ResCSPA, ResCSPB, ResCSPC, ResX,
+                     ResXCSPA, ResXCSPB, ResXCSPC, RobustConv, dw_conv)
 from .detect import Detect, IAuxDetect, IDetect
 
 
@@ -41,19 +42,23 @@ _MODULES = {
     'ImplicitM': ImplicitM, 'Detect': Detect, 'IDetect': IDetect, 'IAuxDetect': IAuxDetect,
     'nn.Conv2d': nn.Conv2d, 'nn.BatchNorm2d': nn.BatchNorm2d, 'nn.Upsample': nn.Upsample,
     'ReOrg': ReOrg, 'DownC': DownC,
+    'dw_conv': dw_conv, 'RobustConv': RobustConv, 'Res': Res, 'ResX': ResX,
+    'ResCSPA': ResCSPA, 'ResCSPB': ResCSPB, 'ResCSPC': ResCSPC,
+    'ResXCSPA': ResXCSPA, 'ResXCSPB': ResXCSPB, 'ResXCSPC': ResXCSPC,
 }
 # Reference modules constructible by its parse_model but used by neither shipped
 # YAML: named here so the error says "out of scope", not "unknown".
 _OUT_OF_SCOPE = {
-    'Chuncat', 'Shortcut', 'Foldcut', 'RobustConv', 'RobustConv2', 'GhostConv', 'Stem',
-    'Res', 'ResX', 'Ghost', 'GhostSPPCSPC', 'GhostStem', 'dw_conv', 'Focus', 'Contract', 'Expand', 'Classify',
+    'Chuncat', 'Shortcut', 'Foldcut', 'RobustConv2', 'GhostConv', 'Stem',
+    'Ghost', 'GhostSPPCSPC', 'GhostStem', 'Focus', 'Contract', 'Expand', 'Classify',
     'TransformerLayer', 'TransformerBlock', 'IBin', 'RepBottleneck',
-} | {f'{p}{s}' for p in ('Res', 'ResX', 'RepRes', 'RepResX', 'Ghost', 'RepBottleneck')
+} | {f'{p}{s}' for p in ('RepRes', 'RepResX', 'Ghost', 'RepBottleneck')
      for s in ('CSPA', 'CSPB', 'CSPC')}
 
-_CONV_LIKE = (nn.Conv2d, Conv, RepConv, DownC, SPP, SPPF, SPPCSPC, Bottleneck, BottleneckCSPA, BottleneckCSPB,
-              BottleneckCSPC)
-_CSP_LIKE = (DownC, SPPCSPC, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC)
+_CONV_LIKE = (nn.Conv2d, Conv, RobustConv, dw_conv, RepConv, DownC, SPP, SPPF, SPPCSPC, Bottleneck, BottleneckCSPA,
+              BottleneckCSPB, BottleneckCSPC, Res, ResCSPA, ResCSPB, ResCSPC, ResX, ResXCSPA, ResXCSPB, ResXCSPC)
+_CSP_LIKE = (DownC, SPPCSPC, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC, ResCSPA, ResCSPB, ResCSPC, ResXCSPA,
+             ResXCSPB, ResXCSPC)
 _ACTS = {'LeakyReLU': nn.LeakyReLU, 'SiLU': nn.SiLU, 'Identity': nn.Identity}
 _CALL_RE = re.compile(r'^(?:nn\.)?(\w+)\((.*)\)$')
 
@@ -295,7 +300,7 @@ class Model(nn.Module):
         engine for that (H, W) derives its power-of-two scales from it. Without
         images a seeded synthetic U[0,1) batch of ``n`` images at ``hw`` is used
         (no calibration set ships with the reference). Returns the record."""
-        from ..engine import Engine
+        from ..engine import Engine, check_plan_precision
         from ..utils.synth import synthetic_images
         if images is None:
             if hw is None:
@@ -307,6 +312,7 @@ class Model(nn.Module):
         # (a pair whose first output has one consumer keeps it on chip and never stores it)
         eng = Engine(self, tuple(images.shape), dev, 'bf16', fuse_pool=False, fuse_pair=False)
         try:
+            check_plan_precision(eng.plan, 'fp8')  # before the calibration forward
             eng.run(images)
             amax = [dict(c=int(b.c), amax=float(b.tensor.abs().max().float())) for b in eng.activation_bufs()]
         finally:
