@@ -247,7 +247,13 @@ def decoded_flip_report(dec_dev, dec_ref, nc, conf, iou):
 # Operands and bias that are small dyadic rationals make every product and every partial sum of a
 # convolution exactly representable in fp32, so the fp32 accumulator holds the true sum whatever the
 # order of the additions, and the stored element must be RNE(true sum) bit for bit.
-_ELT_INT = {torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.float32: torch.int32}
+# torch.float8_e4m3fn (OCP e4m3fn, tests/test_gpu_fp8_exact.py) is an element type here too: sign and
+# seven magnitude bits, codes 0x7F / 0xFF are NaN (never expected, never accepted), no infinities. The
+# +-448 clamp of an e4m3 store is the caller's job: rne refuses a value the cast would turn into NaN.
+E4M3 = torch.float8_e4m3fn
+_ELT_INT = {torch.bfloat16: torch.int16, torch.float16: torch.int16, torch.float32: torch.int32, E4M3: torch.int8}
+_ELT_MAG = {torch.int8: 0x7F, torch.int16: 0x7FFF, torch.int32: 0x7FFFFFFF}
+_NAN_DISTANCE = 1 << 16  # elt_ulps of an e4m3 NaN code: farther than any two finite codes
 
 
 def dyadic(shape, lo, hi, step, gen):
@@ -257,43 +263,61 @@ def dyadic(shape, lo, hi, step, gen):
     return torch.randint(k_lo, k_hi + 1, tuple(shape), generator=gen).double() * step
 
 
+def e4m3_is_nan(t):
+    """Mask of the NaN codes (0x7F, 0xFF) of an e4m3 tensor (or of its uint8 bytes)."""
+    return (t.contiguous().view(torch.uint8) & 0x7F) == 0x7F
+
+
 def rne(t64, dtype):
     """The reference element: torch's CPU cast of the float64 value (round to nearest, ties to even).
     The cast goes through fp32; that is one rounding for every value fp32 holds exactly (all the
     exact-operand sums), and otherwise moves the result only for a value within 2^-24 relative of
-    a rounding boundary."""
-    return t64.to(torch.float64).to(dtype)
+    a rounding boundary. e4m3: the value must already be clamped to +-448."""
+    r = t64.to(torch.float64).to(dtype)
+    if dtype == E4M3:
+        assert not e4m3_is_nan(r).any(), "rne(e4m3): clamp the reference to +-448 first"
+    return r
 
 
 def _elt_key(t):
     """Sign-magnitude bit pattern -> an integer that counts representable values in order."""
     it = _ELT_INT[t.dtype]
     bits = t.contiguous().view(it).to(torch.int64)
-    mag = bits & (0x7FFF if it == torch.int16 else 0x7FFFFFFF)
+    mag = bits & _ELT_MAG[it]
     return torch.where(bits < 0, -mag, mag)
 
 
 def _elt_from_key(key, dtype):
     it = _ELT_INT[dtype]
-    top = 0x8000 if it == torch.int16 else 0x80000000
+    top = _ELT_MAG[it] + 1
     bits = torch.where(key < 0, (-key) | top, key)
     bits = torch.where(bits >= top, bits - 2 * top, bits)  # two's complement of the sign bit
     return bits.to(it).view(dtype)
 
 
 def elt_ulps(got, ref, dtype):
-    """Signed distance got - ref in representable values of ``dtype`` (+0 and -0 coincide)."""
+    """Signed distance got - ref in representable values of ``dtype`` (+0 and -0 coincide). e4m3: ref
+    holds no NaN code, and a NaN code in got is _NAN_DISTANCE away from everything."""
     assert got.dtype == dtype and ref.dtype == dtype
-    return _elt_key(got) - _elt_key(ref)
+    d = _elt_key(got) - _elt_key(ref)
+    if dtype == E4M3:
+        assert not e4m3_is_nan(ref).any(), "an e4m3 NaN code is never expected"
+        d = torch.where(e4m3_is_nan(got), torch.full_like(d, _NAN_DISTANCE), d)
+    return d
 
 
 def elt_neighbours(t64, dtype):
     """(below, above) as float64: the representable values of ``dtype`` that bracket t64
-    (both equal to t64 where it is representable)."""
+    (both equal to t64 where it is representable). e4m3: |t64| <= 448 (rne asserts it), so neither
+    neighbour is ever the NaN code."""
     r = rne(t64, dtype)
     k, r64 = _elt_key(r), r.double()
-    up = _elt_from_key(k + 1, dtype).double()
-    dn = _elt_from_key(k - 1, dtype).double()
+    if dtype == E4M3:  # 448 has no finite neighbour above; it is only ever selected as itself
+        up = _elt_from_key((k + 1).clamp(max=0x7E), dtype).double()
+        dn = _elt_from_key((k - 1).clamp(min=-0x7E), dtype).double()
+    else:
+        up = _elt_from_key(k + 1, dtype).double()
+        dn = _elt_from_key(k - 1, dtype).double()
     lo = torch.where(r64 <= t64, r64, dn)
     hi = torch.where(r64 >= t64, r64, up)
     return lo, hi

@@ -12,6 +12,7 @@ Oracle levels:
     e4m3 keeps 3 mantissa bits per activation and weight, so per-head error is
     bounded at FP8_TOL of max |ref| (measured on MI355X, r02: 0.054-0.095 over the G1 nets,
     0.062-0.086 on yolov7 640 bs 2).
+The bit-exact bar of the same kernels (exact operands, no tolerance) is tests/test_gpu_fp8_exact.py.
 """
 import ctypes
 

@@ -118,3 +118,50 @@ def test_exact_comparator_bites(dtype_name):
     neg = z < 0
     bad_d = got_d.view(torch.int16) != ref_d.view(torch.int16)
     assert int(bad_d[neg].sum()) >= 0.9 * int(neg.sum()) and not bad_d[~neg].any()
+
+
+def test_exact_comparator_bites_e4m3():
+    """The comparator of tests/test_gpu_fp8_exact.py (whole byte buffers against torch's e4m3fn cast of the
+    clamped float64 reference) on one of its cases (tile 35, cin 64, 3x3, act none, both output scales):
+    it must report each of (a) truncation toward zero, (b) round-half-away, (c) a store without the clamp
+    (past 448 the cast gives the NaN code, which helpers.elt_ulps never accepts as a neighbour),
+    (d) subnormals flushed to zero and (e) dq read one channel off -- and nothing on the correct bytes."""
+    import torch
+    from ycx import _lib  # noqa: F401 -- first: a missing library fails this test, it does not skip it
+    import test_gpu_fp8_exact as T
+    from helpers import E4M3, e4m3_is_nan, elt_neighbours, elt_ulps
+    o = T.operands(2, 13, 11, 64, 3, 1, 64)
+    ref = o.z.permute(0, 2, 3, 1).contiguous()  # act none, all 64 channels, NHWC
+    so_hi, so_lo, _ = T.out_scales(ref, "comparator")
+
+    def rejected(got_bytes, so):
+        try:
+            T.assert_bytes(T.framed(got_bytes), T.framed(T.q8(ref, so)), "wrong store")
+        except AssertionError:
+            return int((got_bytes != T.q8(ref, so)).sum())
+        return 0
+
+    for so in (so_hi, so_lo):
+        assert rejected(T.q8(ref, so), so) == 0
+        v = (ref * so).clamp(-448, 448)
+        lo, hi = elt_neighbours(v, E4M3)
+        tie = (lo != hi) & ((v - lo) == (hi - v))
+        trunc = torch.where(v >= 0, lo, hi).to(E4M3).view(torch.uint8)                              # (a)
+        assert rejected(trunc, so) >= 0.05 * v.numel()
+        away = torch.where(tie, torch.where(v >= 0, hi, lo), T.q8(ref, so).view(E4M3).double())     # (b)
+        n_b = rejected(away.to(E4M3).view(torch.uint8), so)
+        assert 0.25 * int(tie.sum()) <= n_b <= int(tie.sum())
+    unclamped = (ref * so_hi).to(E4M3)                                                              # (c)
+    n_nan = int(e4m3_is_nan(unclamped).sum())
+    assert n_nan > 0 and rejected(unclamped.view(torch.uint8), so_hi) == n_nan
+    d = elt_ulps(unclamped, T.q8(ref, so_hi).view(E4M3), E4M3)
+    assert int(d.abs().max()) > 1 and bool((d.abs() > 1)[e4m3_is_nan(unclamped)].all())  # no NaN is "one code away"
+    ok = T.q8(ref, so_lo)                                                                           # (d)
+    flushed = torch.where((ok & 0x78) == 0, ok & 0x80, ok)
+    n_sub = int(((ok & 0x78) == 0).sum() - ((ok & 0x7F) == 0).sum())
+    assert n_sub > 0 and rejected(flushed, so_lo) == n_sub
+    dq = 1.0 / (o.s_w * T.S_X)                                                                       # (e)
+    acc = (ref - o.b) / dq                       # the accumulator, exact
+    off = acc * dq.roll(-1) + o.b                # dq[co + 1] in place of dq[co]
+    for so in (so_hi, so_lo):
+        assert rejected(T.q8(off, so), so) >= 0.5 * ref.numel()
