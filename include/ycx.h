@@ -107,7 +107,9 @@ typedef struct ycx_conv_desc {
   int32_t in_pool;          /* 1: x is the (2h, 2w) map that MP's k2 s2 max-pool reduces to the
                              * (h, w) input (nets/common.py:25-31), pooled in the conv's operand
                              * staging (1x1/s1/p0: 16-bit with cin % 64 == 0, or YCX_DT_FP8
-                             * with cin % 128 == 0, r04); 0: x is the input */
+                             * with cin % 128 == 0, r04), the same pool as ycx_maxpool: in 16-bit a NaN
+                             * in a window makes its pooled pixel NaN in every output channel;
+                             * 0: x is the input */
   int32_t k_split;          /* > 1: the K loop (kh*kw*cin) is cut into k_split contiguous ranges run by
                              * separate workgroups, whose fp32 partial sums go to a caller-owned
                              * workspace (ycx_conv2d_ws, ycx_conv_workspace_size) and are summed in a
@@ -117,8 +119,14 @@ typedef struct ycx_conv_desc {
                              * entry point returns YCX_ERR_UNSUPPORTED */
 } ycx_conv_desc;
 
-/* Max-pool, NHWC, pad value -inf (torch.nn.MaxPool2d semantics, floor mode).
- * YCX_DT_FP8: input and output share one scale (max commutes with it). */
+/* Max-pool, NHWC, torch.nn.MaxPool2d semantics, floor mode. The pad value is -inf, so a window
+ * never comes out below its inputs (a border window of negative values keeps its negative
+ * maximum). NaN propagates as in torch: a 16-bit or fp32 window that holds a NaN gives NaN,
+ * whatever else it holds (the 16-bit range guard relies on it: inf / NaN must reach the heads
+ * through a bare MP / SP too). The sign of a zero maximum is not specified.
+ * YCX_DT_FP8: input and output share one scale (max commutes with it). e4m3 activations hold
+ * neither NaN (codes 0x7F / 0xFF) nor infinities: the fp8 stores saturate and cannot produce
+ * them, so the result for such a code is unspecified. */
 typedef struct ycx_pool_desc {
   int32_t n, h, w, c, in_c_off, in_c_stride;
   int32_t ho, wo, out_c_off, out_c_stride;

@@ -914,7 +914,7 @@ __global__ void __launch_bounds__(WM * WN * 64) conv_bf16_glds(ConvArgs a, HeadA
       eltx8 v;
 #pragma unroll
       for (int j = 0; j < 8; ++j)
-        v[j] = (elt_t)fmaxf(fmaxf((float)pw[i][0][j], (float)pw[i][1][j]), fmaxf((float)pw[i][2][j], (float)pw[i][3][j]));
+        v[j] = (elt_t)ycx_pool_max(ycx_pool_max((float)pw[i][0][j], (float)pw[i][1][j]), ycx_pool_max((float)pw[i][2][j], (float)pw[i][3][j]));
       if (b_base[i] < 0) v = eltx8{};
       *reinterpret_cast<eltx8*>(base + (wid + NW * i) * 1024 + lane * 16) = v;
     }
@@ -3215,7 +3215,7 @@ __device__ __forceinline__ void wres_pair_body(const ConvArgs& a, const ConvArgs
       eltx8 v;
 #pragma unroll
       for (int j = 0; j < 8; ++j)
-        v[j] = (elt_t)fmaxf(fmaxf((float)pw[0][j], (float)pw[1][j]), fmaxf((float)pw[2][j], (float)pw[3][j]));
+        v[j] = (elt_t)ycx_pool_max(ycx_pool_max((float)pw[0][j], (float)pw[1][j]), ycx_pool_max((float)pw[2][j], (float)pw[3][j]));
       *reinterpret_cast<eltx8*>(p1s + (ch >> 3) * P1_SLAB + pc * 128 + (((ch & 7) ^ swz<64>(pc)) << 4)) = v;
     }
     // second conv on the y1 tile

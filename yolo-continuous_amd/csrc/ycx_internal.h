@@ -59,6 +59,15 @@ __device__ __forceinline__ bool ycx_bounds_ok(bool ok, int line) {
 #define YCX_BOUNDS_OK(lo, n, lim) true
 #endif
 
+// The max of every 16-bit and fp32 max-pool (ycx_maxpool's kernels, the in_pool staging of the
+// LDS-DMA 1x1 and the pair-pool's y1 tile): torch.nn.MaxPool2d's, NaN when either operand is NaN.
+// fmaxf returns the other operand, so a pool would turn a window with a NaN back into a finite
+// number (an all-NaN one into the accumulator's -inf) and the 16-bit range guard, which relies on
+// inf / NaN reaching the heads, could be defeated by a bare MP / SP. gfx950 has the instruction
+// (v_maximum3_f32, v_pk_maximum3_f16): one op per max as before, and the same value as fmaxf
+// whenever neither operand is NaN.
+__device__ __forceinline__ float ycx_pool_max(float a, float b) { return __builtin_elementwise_maximum(a, b); }
+
 // Activation applied in the conv epilogues (Conv.act, nets/common.py:103).
 // FAST (bf16 outputs): the raw v_exp_f32 (2^x, no range fix-up: overflow to
 // inf gives rcp 0, i.e. silu -> 0) and v_rcp_f32, ~1 ulp fp32, far below bf16

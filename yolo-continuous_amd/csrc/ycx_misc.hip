@@ -59,7 +59,7 @@ __global__ void __launch_bounds__(256) maxpool_kernel(ycx_pool_desc d, const T* 
         V v = *reinterpret_cast<const V*>(x + (((size_t)n * d.h + iy) * d.w + ix) * d.in_c_stride +
                                           d.in_c_off + c * VN);
 #pragma unroll
-        for (int j = 0; j < VN; ++j) m[j] = fmaxf(m[j], (float)v[j]);
+        for (int j = 0; j < VN; ++j) m[j] = ycx_pool_max(m[j], (float)v[j]);
       }
     V o;
 #pragma unroll
@@ -92,7 +92,7 @@ __global__ void __launch_bounds__(256) maxpool_rows_kernel(ycx_pool_desc d, cons
     for (int ix = xa; ix < xb; ++ix) {
       const V v = *reinterpret_cast<const V*>(rowp + (size_t)ix * d.in_c_stride);
 #pragma unroll
-      for (int j = 0; j < VN; ++j) m[j] = fmaxf(m[j], (float)v[j]);
+      for (int j = 0; j < VN; ++j) m[j] = ycx_pool_max(m[j], (float)v[j]);
     }
   }
   V o;
@@ -223,6 +223,12 @@ __global__ void __launch_bounds__(256) quantize_f8_kernel(const float* __restric
 // (image, CC-channel slice) holds the whole H x W plane in LDS (raw elements), and each level
 // is a row pass then a column pass (a k x k max with -inf padding is separable); level i goes
 // to channels out_c_off + i*c. E = bytes per element (2 bf16 / fp16 (HALF), 1 e4m3); 16-byte chunks.
+// e4m3 activations hold no NaN (the fp8 stores saturate): the fp8 cascade keeps fmaxf
+template <int E>
+__device__ __forceinline__ float pool_max_e(float a, float b) {
+  if constexpr (E == 1) return fmaxf(a, b);
+  else return ycx_pool_max(a, b);
+}
 template <int E, bool HALF = false>
 __device__ __forceinline__ void chunk_to_f(uint4 v, float (&f)[16 / E]) {
   if constexpr (E == 2 && HALF) {
@@ -285,7 +291,7 @@ __global__ void __launch_bounds__(256) maxpool_cascade_kernel(ycx_pool_desc d, i
       for (int xi = max(xx - r, 0); xi <= min(xx + r, W - 1); ++xi) {
         chunk_to_f<E, HALF>(S[(yy * W + xi) * nchunk + g], f);
 #pragma unroll
-        for (int j = 0; j < NE; ++j) m[j] = fmaxf(m[j], f[j]);
+        for (int j = 0; j < NE; ++j) m[j] = pool_max_e<E>(m[j], f[j]);
       }
       T[i] = f_to_chunk<E, HALF>(m);
     }
@@ -298,7 +304,7 @@ __global__ void __launch_bounds__(256) maxpool_cascade_kernel(ycx_pool_desc d, i
       for (int yi = max(yy - r, 0); yi <= min(yy + r, H - 1); ++yi) {
         chunk_to_f<E, HALF>(T[(yi * W + xx) * nchunk + g], f);
 #pragma unroll
-        for (int j = 0; j < NE; ++j) m[j] = fmaxf(m[j], f[j]);
+        for (int j = 0; j < NE; ++j) m[j] = pool_max_e<E>(m[j], f[j]);
       }
       const uint4 v = f_to_chunk<E, HALF>(m);
       S[i] = v;  // the next level's source (every row pass read of S is behind the barrier above)
