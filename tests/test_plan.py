@@ -52,30 +52,31 @@ def test_plan_yolov7_layout():
 
 
 def test_pool_fusion_pass_finds_the_mp_blocks():
-    """The engine's MP-pool fusion pass (host logic, no GPU): every yolov7 k2 s2 pool feeds
+    """The schedule's MP-pool fusion pass (host logic, no GPU): every yolov7 k2 s2 pool feeds
     exactly one 1x1 / s1 conv and is fused into it (bf16, and fp8 where cin % 128 == 0: all five);
     in yolov7-tiny only pools read by a lone 1x1 fuse; f32 plans and fuse_pool=False keep every pool."""
-    from ycx import _lib as L
-    from ycx.engine import Engine
+    from ycx.schedule import Schedule
 
-    def pairs(net, nc, dt=L.DT_BF16, fuse=True):
+    def pairs(net, nc, precision='bf16', fuse=True):
+        """The pool of every 'conv' launch that has one (at bs 2 no conv pair takes a pooled conv)."""
         plan = Plan(Model(cvt_cfg(net), ANCHORS, nc), (2, 3, 640, 640))
-        eng = Engine.__new__(Engine)  # the pass reads the plan graph and the plan dtype only
-        eng.graph, eng.dt, eng.fuse_pool = plan.graph, dt, fuse
-        return eng._pool_convs()
+        sched = Schedule(plan, precision, fuse_pool=fuse)
+        got = [la.nodes for la in sched.launches if la.kind == 'conv' and len(la.nodes) > 1]
+        assert all(pool.out.consumers == [conv] for conv, pool in got)
+        return [pool for _, pool in got]
 
     got = pairs('yolov7', 80)
     assert len(got) == 5
-    for pool in got.values():
+    for pool in got:
         p = pool.p
         assert (p['k'], p['s'], p['p']) == (2, 2, 0) and pool.inputs[0].h == 2 * pool.out.h
         (conv,) = pool.out.consumers
         assert conv.kind == 'conv' and (conv.p['k'], conv.p['s'], conv.p['p']) == (1, 1, 0)
-    f8 = pairs('yolov7', 80, dt=L.DT_FP8)
-    assert len(f8) == 5 and all(int(pool.out.consumers[0].p['w'].shape[1]) % 128 == 0 for pool in f8.values())
-    assert pairs('yolov7', 80, dt=L.DT_F32) == {}
-    assert pairs('yolov7', 80, fuse=False) == {}
-    for pool in pairs('yolov7-tiny', 1).values():
+    f8 = pairs('yolov7', 80, precision='fp8')
+    assert len(f8) == 5 and all(int(pool.out.consumers[0].p['w'].shape[1]) % 128 == 0 for pool in f8)
+    assert pairs('yolov7', 80, precision='f32') == []
+    assert pairs('yolov7', 80, fuse=False) == []
+    for pool in pairs('yolov7-tiny', 1):
         assert pool.out.consumers[0].p['k'] == 1
 
 

@@ -13,10 +13,12 @@ Lowering (once per input shape / device / precision):
    max with -inf padding); every concat input that a kernel produces is written
    straight into its channel slice of the concat buffer (Concat costs nothing;
    a copy kernel runs only for inputs that cannot alias).
-3. Allocate one NHWC device buffer per remaining value (no reuse: a yolov7
-   bs=32 640x640 plan is ~10 GB of bf16 activations, small next to 288 GB HBM),
-   pack weights ([cout_pad][kh][kw][cin], bf16 or fp32) and build the ctypes
-   op array consumed by the native loop ``ycx_run_ops`` (or a HIP graph).
+3. Bind the schedule to memory: ``schedule.Schedule`` decides, without a device, which launches
+   run the graph (stem pair, conv pair and trio, pooled 1x1, pool cascade) and which buffers
+   they need. Allocate one NHWC device buffer per value (no reuse: a yolov7 bs=32 640x640 plan
+   is ~10 GB of bf16 activations, small next to 288 GB HBM), pack weights ([cout_pad][kh][kw][cin],
+   bf16 or fp32) and emit one op per launch into the ctypes array consumed by the native loop
+   ``ycx_run_ops`` (or a HIP graph).
 """
 from __future__ import annotations
 
@@ -32,6 +34,7 @@ from . import _lib as L
 from .nets.common import (SP, SPP, SPPCSPC, SPPF, MP, Bottleneck, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC,
                           Concat, Conv, DownC, ReOrg, RepConv, Res, RobustConv)
 from .nets.detect import Detect, IAuxDetect, IDetect
+from .schedule import Schedule, cascade_fits, cout_pad  # noqa: F401  (cascade_fits: re-exported)
 
 
 class Buf:
@@ -361,19 +364,6 @@ _NO_KSPLIT = bool(os.environ.get('YCX_NO_KSPLIT'))
 _NO_SILU_PS = bool(os.environ.get('YCX_NO_SILU_PS'))
 
 
-def cascade_fits(h, w, c, esz):
-    """Whether ycx_maxpool's one-launch cascade (levels > 1) takes an (h, w) map of c
-    channels of esz bytes: it keeps two copies of the H x W plane of one channel
-    slice (a 16-byte multiple dividing c, at most 128 channels) in 64 KB of LDS
-    (ycx_misc.hip, ycx_maxpool). Mirrors the launcher's slice search exactly."""
-    t = 128
-    while t * esz >= 16:
-        if c % t == 0 and 2 * h * w * t * esz <= 65536:
-            return True
-        t >>= 1
-    return False
-
-
 class Plan:
     """Device-independent lowering of a Model for one input shape: the graph
     after all passes, its outputs and its algorithmic FLOPs."""
@@ -555,10 +545,7 @@ class Engine:
         self.dtype = {'bf16': torch.bfloat16, 'f32': torch.float32, 'fp8': torch.float8_e4m3fn,
                       'fp16': torch.float16}[precision]
         self.dt = {'bf16': L.DT_BF16, 'f32': L.DT_F32, 'fp8': L.DT_FP8, 'fp16': L.DT_F16}[precision]
-        self.fuse_stem2 = fuse_stem2
-        self.fuse_pool = fuse_pool  # False: every pool writes its map (fp8 calibration reads them all)
-        self.fuse_pair = fuse_pair  # False: every 1x1 of a pair stores its map (fp8 calibration reads them all)
-        self.fuse_pair_pool = fuse_pair_pool  # False: a pair stores its first map for the MP branch's pooled 1x1
+        self.schedule = Schedule(self.plan, precision, fuse_stem2, fuse_pool, fuse_pair, fuse_pair_pool)
         self.prepacked = prepacked  # {'p<i>': packed tensor} from ycx.prepack (skips folding / packing)
         self.graph_exec = None
         self.graph, self.out_vals, self.is_list = self.plan.graph, self.plan.out_vals, self.plan.is_list
@@ -569,23 +556,10 @@ class Engine:
             self._assign_fp8_scales(fp8_amax)
         self._build()
 
-    @property
-    def h16(self):
-        """The plan runs the 16-bit MFMA kernels (bf16 or IEEE half elements)."""
-        return self.dt in (L.DT_BF16, L.DT_F16)
-
     def activation_bufs(self):
         """The plan's activation buffers in allocation order (the order of
         ``self.buffers``; fp8 calibration keys its amax list on it)."""
-        skip_vals = {id(nd.out) for nd in self.graph.nodes if id(nd) in self._stem2_pairs()}
-        bufs, seen = [], set()
-        for node in self.graph.nodes:
-            for v in [node.out] + node.inputs:
-                b = v.buf
-                if b is not None and id(b) not in seen and id(v) not in skip_vals:
-                    seen.add(id(b))
-                    bufs.append(b)
-        return bufs
+        return self.schedule.activation_bufs
 
     def _assign_fp8_scales(self, amax):
         """One power-of-two scale per group of buffers tied by a pool or a copy
@@ -621,129 +595,19 @@ class Engine:
     def _scale(self, v):
         return self.scales.get(id(v.buf), 1.0) if v.buf is not None else 1.0
 
-    def _cout_pad(self, cout, stem=False):
-        if self.dt == L.DT_F32:
-            return -(-cout // 64) * 64
-        if self.dt == L.DT_FP8 and not stem:
-            return -(-cout // 64) * 64
-        if cout <= 32:
-            return 32
-        if cout <= 64:
-            return 64
-        return -(-cout // 128) * 128
-
-    def _stem2_pairs(self):
-        """Stem -> 3x3/s2 conv pairs that run as one ycx_stem_conv2 (the stem
-        map stays in LDS): bf16, the stem's output read by that conv only."""
-        pairs = {}
-        if not (self.h16 or self.dt == L.DT_FP8) or not self.fuse_stem2:
-            return pairs
-        for nd in self.graph.nodes:
-            if nd.kind != 'stem':
-                continue
-            v, p = nd.out, nd.p
-            if v.role != 'act' or len(v.consumers) != 1 or v.buf is None or v.buf.c != v.c:
-                continue
-            c = v.consumers[0]
-            q = c.p
-            if c.kind != 'conv' or c.inputs[0] is not v or q['residual'] is not None or q['layout'] != L.OUT_NHWC:
-                continue
-            if not (p['k'] == 3 and p['p'] == 1 and p['s'] in (1, 2) and int(p['w'].shape[1]) == 3 and
-                    int(p['w'].shape[0]) == 32 and p['layout'] == L.OUT_NHWC):
-                continue
-            if not (q['k'] == 3 and q['s'] == 2 and q['p'] == 1 and int(q['w'].shape[0]) <= 64 and
-                    int(q['w'].shape[0]) % 8 == 0 and q['ho'] % 4 == 0 and q['wo'] % 32 == 0):
-                continue
-            if p['act'] != q['act']:  # the fused kernel is instantiated per (act, act) with both equal
-                continue
-            pairs[id(nd)] = c
-        return pairs
-
-    def _conv_pairs(self, pooled):
-        """1x1 -> 1x1 chains that run as one ycx_conv2d_pair launch (tile 55): a 1x1 / s1
-        conv with cin 64 / 128 / 256 and 256 output channels on a map large enough for the
-        weight-resident kernel (>= 8 64-pixel tiles per CU), whose output a second 1x1 / s1
-        conv (cin 256, cout_pad 128 / 256) reads directly; the first conv's output is still
-        stored when anything else reads it (yolov7: layer 11 -> layer 14 at 160^2, layer 11
-        also feeding the MP branch). 16-bit plans; YCX_NO_CONV_PAIR=1 keeps them apart.
-        Returns {id(first conv): second conv}."""
-        out = {}
-        if not self.h16 or not self.fuse_pair or os.environ.get('YCX_NO_CONV_PAIR'):
-            return out
-        taken = set()
-
-        def pointwise(nd):
-            q = nd.p
-            return (nd.kind == 'conv' and q['k'] == 1 and q['s'] == 1 and q['p'] == 0 and q['residual'] is None and
-                    q['layout'] == L.OUT_NHWC and id(nd) not in pooled)
-
-        for a in self.graph.nodes:
-            if not pointwise(a) or id(a) in taken:
-                continue
-            x, v = a.inputs[0], a.out
-            cin, cout = int(a.p['w'].shape[1]), int(a.p['w'].shape[0])
-            if cin not in (64, 128, 256) or cout != 256 or v.role != 'act' or v.buf is None:
-                continue
-            if x.n * x.h * x.w < 8 * 64 * 256 or (x.role != 'input' and (x.coff % 8 or x.buf.c % 8)):
-                continue
-            if len(v.consumers) > 1 and (v.coff % 8 or v.buf.c % 8):  # y1 is stored: ycx_conv2d_pair's 16-B stores
-                continue
-            for b in v.consumers:
-                if not pointwise(b) or b.inputs[0] is not v or id(b) in taken or id(b) in out:
-                    continue
-                cb = int(b.p['w'].shape[0])
-                if self._cout_pad(cb) not in (128, 256) or cb % 8:
-                    continue
-                if b.out.role == 'act' and (b.out.coff % 8 or b.out.buf.c % 8):
-                    continue
-                out[id(a)] = b
-                taken.update((id(a), id(b)))
-                break
-        return out
-
-    def _pair_pools(self, chains, pooled):
-        """Pairs (``_conv_pairs``) that also run the MP branch's 1x1 (ycx_conv2d_pair_pool): the
-        first conv's only other reader is a k2 s2 max-pool already fused into its 1x1 conv c
-        (``_pool_convs``), c is 256 -> cout_pad 128 with an NHWC output on 8-channel bounds, and the
-        map is h even, w % 32 == 0 (yolov7: layer 11 -> 14 with 12 -> 13). The 256-channel map is then
-        neither stored nor read back. Off with the pair, or with ``fuse_pair_pool=False``.
-        Returns {id(first conv): (pooled conv c, its pool node)}."""
-        out = {}
-        if not self.fuse_pair_pool:
-            return out
-        by_pool = {id(pl): c for c, pl in ((c, pooled[id(c)]) for c in self.graph.nodes if id(c) in pooled)}
-        for a in self.graph.nodes:
-            b = chains.get(id(a))
-            if b is None:
-                continue
-            v = a.out
-            rest = [nd for nd in v.consumers if nd is not b]
-            if len(rest) != 1 or id(rest[0]) not in by_pool or v.role != 'act' or v.h % 2 or v.w % 32:
-                continue
-            c = by_pool[id(rest[0])]
-            q, cc = c.p, int(c.p['w'].shape[0])
-            if int(q['w'].shape[1]) != 256 or self._cout_pad(cc) != 128 or cc % 8 or q['residual'] is not None:
-                continue
-            if q['layout'] != L.OUT_NHWC or c.out.role != 'act' or c.out.coff % 8 or c.out.buf.c % 8:
-                continue
-            out[id(a)] = (c, rest[0])
-        return out
-
-    def _pair_op(self, a, b, c=None, pool=None):
-        """One OP_CONV_PAIR for the chain a -> b (``_conv_pairs``); with c (``_pair_pools``) also the
-        1x1 conv on the max-pool of a's output."""
+    def _pair_op(self, a, b, c=None, pool=None, store_a=False):
+        """One OP_CONV_PAIR for the chain a -> b (``schedule.conv_pairs``); with c (``schedule.pair_pools``)
+        also the 1x1 conv on the max-pool of a's output. store_a: a's map is written."""
         da, wa, ba, fa, shape = self._conv_parts(a)
         db, wb, bb, fb, _ = self._conv_parts(b)
         op = L.Op()
         op.kind = L.OP_CONV_PAIR
         op.d.pair[0], op.d.pair[1] = da, db
         idx = len(self.op_info)
-        v = a.out
-        store_a = len(v.consumers) > 1 and c is None
         op.in_ = self._val_ptr(a.inputs[0], idx, 'in_')
         op.weight, op.bias = wa.data_ptr(), ba.data_ptr()
         op.weight2, op.bias2 = wb.data_ptr(), bb.data_ptr()
-        op.out = self._val_ptr(v, idx, 'out') if store_a else None
+        op.out = self._val_ptr(a.out, idx, 'out') if store_a else None
         op.out2 = self._val_ptr(b.out, idx, 'out2')
         isz = self.dtype.itemsize
         nbytes = (self._conv_bytes(da, wa, out_bytes=store_a) +
@@ -770,46 +634,19 @@ class Engine:
         self.packed = {}
         self._conv_index = {id(nd): i for i, nd in enumerate(
             nd for nd in self.graph.nodes if nd.kind in ('conv', 'stem', 'stem_reorg', 'gconv'))}
-        pairs = self._stem2_pairs()
-        fused = {id(c) for c in pairs.values()}
-        for b in self.activation_bufs():  # the stem maps of fused stem2 pairs stay in LDS
+        for b in self.schedule.activation_bufs:
             b.tensor = torch.empty((b.n, b.h, b.w, b.c), dtype=dt, device=dev)
             self.buffers.append(b.tensor)
-        ops, self.input_slots, self.output_slots, self.op_info = [], [], {}, []
+        self.input_slots, self.output_slots, self.op_info = [], {}, []
         self._ksplit_ops = []  # (op index, workspace bytes) of the split-K convs
         self.conv_flops = 0
-        cascades = self._pool_cascades()
-        for c in cascades.values():
-            fused.update(id(nd) for nd in c[1:])
-        pooled = self._pool_convs()  # {id(conv): pool node} (the pool runs inside the conv)
-        fused.update(id(nd) for nd in pooled.values())
-        chains = self._conv_pairs(pooled)  # {id(first 1x1): second 1x1} (one launch each)
-        fused.update(id(nd) for nd in chains.values())
-        trios = self._pair_pools(chains, pooled)  # {id(first 1x1): (pooled 1x1, pool)} (in the pair's launch)
-        fused.update(id(c) for c, _ in trios.values())
-        for node in self.graph.nodes:
-            k = node.kind
-            if id(node) in fused:
-                continue
-            if id(node) in pairs:
-                ops.append(self._stem2_op(node, pairs[id(node)]))
-            elif id(node) in chains:
-                ops.append(self._pair_op(node, chains[id(node)], *trios.get(id(node), ())))
-            elif k in ('conv', 'stem', 'stem_reorg'):
-                ops.append(self._conv_op(node, pool=pooled.get(id(node))))
-            elif k == 'gconv':
-                ops.append(self._gconv_op(node))
-            elif k == 'pool':
-                ops.append(self._pool_op(node, levels=len(cascades.get(id(node), [node]))))
-            elif k == 'up':  # an unfused upsample may write a slice of a concat buffer
-                ops.append(self._copy_op(node.inputs[0], node.out, node.out.coff, scale=2))
-            elif k == 'concat':
-                for v, off in node.p['copies']:
-                    ops.append(self._copy_op(v, node.out, off, scale=1))
-            elif k == 'tonchw':
-                ops.append(self._copy_op(node.inputs[0], node.out, 0, scale=1, nchw=True))
-            else:
-                raise AssertionError(k)
+        emit = {'stem2': lambda la: self._stem2_op(*la.nodes),
+                'conv_pair': lambda la: self._pair_op(*la.nodes, store_a=la.store_a),
+                'conv': lambda la: self._conv_op(*la.nodes),
+                'gconv': lambda la: self._gconv_op(*la.nodes),
+                'pool': lambda la: self._pool_op(la.nodes[0], levels=la.levels),
+                'copy': lambda la: self._copy_op(la.src, la.dst, la.off, la.scale, nchw=la.nchw)}
+        ops = [emit[la.kind](la) for la in self.schedule.launches]
         self.n_ops = len(ops)
         self.ops = (L.Op * max(1, self.n_ops))(*ops)
         # one fp32 workspace for every split-K conv of the plan (they run in turn on its stream)
@@ -836,12 +673,12 @@ class Engine:
         """Packed weights/bias (kept alive in self.params) and the descriptor of a conv/stem node.
         bf16_weights: 16-bit packing whatever the plan dtype (the fp8 stem2 pair computes in bf16;
         an fp16 plan's pair in fp16).
-        pool: the k2 s2 pool node feeding this 1x1 conv, fused into it (``_pool_convs``)."""
+        pool: the k2 s2 pool node feeding this 1x1 conv, fused into it (``schedule.pool_convs``)."""
         p, x, out = node.p, node.inputs[0], node.out
         w64, b64 = p['w'], p['b']
         cout, cin, k = int(w64.shape[0]), int(w64.shape[1]), p['k']
         stem = node.kind in ('stem', 'stem_reorg')
-        cpad = self._cout_pad(cout, stem or bf16_weights)
+        cpad = cout_pad(self.precision, cout, stem or bf16_weights)
         f8 = self.dt == L.DT_FP8
         if stem:  # [kh][kw][cin][cout_pad] fp32
             wshape, wdt = (k, k, cin, cpad), torch.float32
@@ -1033,69 +870,6 @@ class Engine:
         self.op_info.append(dict(kind='stem2', name='stem2_fused', flops=fs + fc, shape=shape, parts=2, bytes=nbytes))
         return op
 
-    def _pool_cascades(self):
-        """Chains of 'same' stride-1 pools (the SPPCSPC k5 cascade, `pyramid`), each pool
-        reading the previous one's output, written to adjacent slices of one buffer: run as
-        one ycx_maxpool launch with levels = chain length (bf16 / fp8 plans, HIP_CASCADE
-        kernel), when the map's plane fits the kernel's LDS (``cascade_fits``; larger maps,
-        e.g. the stride-32 map of a 1472^2 input, keep one launch per pool).
-        Returns {id(first pool): [pool nodes]}."""
-        if not (self.h16 or self.dt == L.DT_FP8) or os.environ.get('YCX_NO_POOL_CASCADE'):
-            return {}
-        nodes, out = self.graph.nodes, {}
-        used = set()
-
-        def same_pool(nd):
-            p = nd.p
-            return nd.kind == 'pool' and p['s'] == 1 and p['k'] % 2 == 1 and p['p'] == p['k'] // 2
-
-        for i, a in enumerate(nodes):
-            if id(a) in used or not same_pool(a) or a.out.role in ('input', 'output'):
-                continue
-            if not cascade_fits(a.inputs[0].h, a.inputs[0].w, a.inputs[0].c, self.dtype.itemsize):
-                continue
-            chain = [a]
-            for b in nodes[i + 1:]:
-                prev = chain[-1]
-                if not (same_pool(b) and b.p['k'] == a.p['k'] and b.inputs[0] is prev.out and
-                        b.out.buf is a.out.buf and b.out.coff == prev.out.coff + prev.out.c and
-                        b.out.role not in ('input', 'output')):
-                    break
-                chain.append(b)
-            if len(chain) > 1:
-                out[id(a)] = chain
-                used.update(id(nd) for nd in chain)
-        return out
-
-    def _pool_convs(self):
-        """MP's k2 s2 pools (nets/common.py:25-31) whose map is read only by one 1x1 / s1
-        conv: the conv pools its operand while staging it (ycx_conv_desc.in_pool, 16-bit
-        plans, and fp8 plans where cin % 128 == 0), so the pooled map is never written.
-        yolov7: all five MP pools. Returns {id(conv node): pool node}."""
-        fp8 = self.dt == L.DT_FP8
-        if not (self.h16 or fp8) or not self.fuse_pool or os.environ.get('YCX_NO_POOL_FUSE'):
-            return {}
-        out = {}
-        for nd in self.graph.nodes:
-            if nd.kind != 'pool':
-                continue
-            p, x, v = nd.p, nd.inputs[0], nd.out
-            if not (p['k'] == 2 and p['s'] == 2 and p['p'] == 0 and x.h == 2 * v.h and x.w == 2 * v.w):
-                continue
-            if x.role != 'act' or v.role != 'act' or len(v.consumers) != 1 or x.coff % 8 or x.buf.c % 8:
-                continue
-            c = v.consumers[0]
-            q = c.p
-            if c.kind != 'conv' or c.inputs[0] is not v or not (q['k'] == 1 and q['s'] == 1 and q['p'] == 0):
-                continue
-            cin, cout = int(q['w'].shape[1]), int(q['w'].shape[0])
-            if cin % (128 if fp8 else 64) or self._cout_pad(cout) % 64 or q['layout'] == L.OUT_NCHW_F32:
-                continue
-            if x.n * x.h * x.w * x.buf.c * (1 if fp8 else 2) >= (1 << 31) - 64:
-                continue
-            out[id(c)] = nd
-        return out
-
     def _pool_op(self, node, levels=1):
         x, out, p = node.inputs[0], node.out, node.p
         d = L.PoolDesc()
@@ -1147,7 +921,7 @@ class Engine:
     def head_ops(self):
         """Op index of each output's producing conv, when every output is a bf16 or
         e4m3 Detect-head 1x1 conv the fused kernels cover (ycx_conv2d_head), else None."""
-        if not (self.h16 or self.dt == L.DT_FP8):
+        if self.dt == L.DT_F32:
             return None
         f8 = self.dt == L.DT_FP8
         idx = []
