@@ -15,6 +15,8 @@
  *                       IDetect conv + ImplicitA/M (folded)     nets/idetect.py:26-31
  *   ycx_conv2d_grouped  Conv with g > 1 (small groups, depthwise) nets/common.py:97-109
  *                       dw_conv                                 nets/common.py:20-22
+ *                       RobustConv2's strided depthwise half     nets/common.py:132
+ *   ycx_deconv2d        nn.ConvTranspose2d, kernel == stride     nets/common.py:133-134 (RobustConv2)
  *   ycx_stem_conv       first Conv on the fp32 NCHW image       nets/common.py:105-106 (Cin=3)
  *   ycx_stem_conv2      first two Convs fused (3->32, then 3x3   cfg/net/yolov7.yaml:7-8,
  *                       stride 2 -> 64); the stem output stays   nets/common.py:97-109
@@ -46,7 +48,8 @@ extern "C" {
 #endif
 
 /* The version stays 9 across the `groups` field appended to ycx_conv_desc (and the
- * ycx_conv2d_grouped / YCX_OP_GCONV additions): the library and its ctypes mirror
+ * ycx_conv2d_grouped / YCX_OP_GCONV additions) and across ycx_deconv2d / YCX_OP_DECONV, which add
+ * an entry point and an op kind but no struct and no field: the library and its ctypes mirror
  * (ycx/_lib.py) are always built together in-tree and check each other's struct sizes
  * (ycx_struct_size, ids 0 to 11 unchanged) at load time; a zero-initialised descriptor
  * means what it meant before. */
@@ -232,7 +235,8 @@ typedef struct ycx_head_desc {
 enum { YCX_OP_CONV = 1, YCX_OP_STEM = 2, YCX_OP_POOL = 3, YCX_OP_COPY = 4, YCX_OP_STEM2 = 5, YCX_OP_HEAD = 6,
        YCX_OP_CONV_PAIR = 7,
        YCX_OP_STEM_REORG = 8 /* ycx_stem_conv_reorg: d.conv, in, weight, bias, out */,
-       YCX_OP_GCONV = 9 /* ycx_conv2d_grouped: d.conv, in, weight (fp32), bias, out, residual */ };
+       YCX_OP_GCONV = 9 /* ycx_conv2d_grouped: d.conv, in, weight (fp32), bias, out, residual */,
+       YCX_OP_DECONV = 10 /* ycx_deconv2d: d.conv, in, weight, bias, out */ };
 typedef struct ycx_op {
   int32_t kind;
   int32_t pad_;
@@ -291,16 +295,40 @@ ycx_status ycx_conv2d(const ycx_conv_desc* d, const void* x, const void* w,
  * direct NHWC conv, VALU FMA with fp32 accumulation in a fixed order (kernel row, kernel column,
  * input channel of the group), for the small groups the MFMA tiles cannot take:
  *   cin_g = cin / groups == cout_g = cout / groups, cin_g in {1, 2, 4, 8, 16} (1: depthwise);
- *   kh == kw in {3, 5, 7}, stride 1 or 2, pad == kh / 2; dtype bf16 / fp16 / f32.
+ *   kh == kw in {3, 5, 7}, stride 1 or 2, pad == kh / 2; dtype bf16 / fp16 / f32;
+ *   depthwise only (cin_g == 1) also kh == kw == 11 and stride 4 or 8 (RobustConv2's strided half,
+ *   nets/common.py:128-132: [32, 7, 4], [32, 11, 8]), any of k in {3, 5, 7, 11} with any of s in {1, 2, 4, 8}.
  * x, y, residual: NHWC channel slices as ycx_conv2d (in_c_*, out_c_*, res_c_*; offsets, strides and
  * cout multiples of 8: a lane owns a 16-byte vector of 16-bit channels); cout_pad and tile are not used.
  * w: fp32 in every dtype, [kh][kw][cout][cin_g], unscaled; bias: fp32 [cout].
  * y = act(acc + bias) (+ residual), act YCX_ACT_NONE / SILU / LEAKY; 16-bit stores round to nearest
  * even. Only YCX_OUT_NHWC, no in_pool, no k_split, no YCX_ACT_SILU_PS, no fp8: YCX_ERR_UNSUPPORTED,
  * as is any other shape. Null pointers and inconsistent shapes (ho / wo, a slice past its stride,
- * cin % groups != 0): YCX_ERR_BAD_ARG before any device call. */
+ * cin % groups != 0): YCX_ERR_BAD_ARG before any device call. The descriptor is judged before the data
+ * pointers: a null x / w / bias / y reports YCX_ERR_BAD_ARG only with a descriptor the kernel takes. */
 ycx_status ycx_conv2d_grouped(const ycx_conv_desc* d, const void* x, const float* w, const float* bias,
                               void* y, const void* residual, void* stream);
+/* Transposed convolution with kernel == stride (nn.ConvTranspose2d(cin, cout, s, s, padding 0,
+ * output_padding 0, dilation 1, groups 1, bias), nets/common.py:133-134): the learned x-s upsample,
+ *   y[n][oh][ow][co] = act(bias[co] + sum_ci x[n][oh / s][ow / s][ci] * W[ci][co][oh % s][ow % s]).
+ * d is a ycx_conv_desc with kh == kw == stride == s in {2, 4, 8}, pad == 0, ho == h * s, wo == w * s,
+ * groups 0 or 1; cout_pad, tile and the res_* fields are not used. The windows do not overlap, so this
+ * is one GEMM (rows s*s*cout, columns n*h*w, K = cin) whose tiles are stored straight to their s x s
+ * output blocks: no intermediate reaches memory.
+ * x, y: NHWC channel slices as ycx_conv2d (in_c_*, out_c_*; cin, cout, offsets and strides multiples
+ * of 8: 16-byte vectors), so y may be a slice of a concat buffer.
+ * w: packed [s*s][cout][cin] in the activation dtype (bf16 / fp16 / f32), tap = (oh % s) * s + (ow % s),
+ *    i.e. torch's weight[ci][co][dy][dx] permuted (2, 3, 1, 0); bias: fp32 [cout]. Unscaled: a SiLU
+ *    epilogue is the plain YCX_ACT_SILU.
+ * 16-bit: MFMA with fp32 accumulation over ci in a fixed order; f32: one fmaf per ci, ascending.
+ * act YCX_ACT_NONE / SILU / LEAKY; 16-bit stores round to nearest even.
+ * YCX_ERR_BAD_ARG before any device call: null pointers, n <= 0, ho / wo not h * s / w * s, a slice
+ * past its stride. YCX_ERR_UNSUPPORTED: kh != stride, s not in {2, 4, 8}, pad != 0, fp8,
+ * YCX_ACT_SILU_PS, an out_layout other than YCX_OUT_NHWC, in_pool, k_split > 1, groups > 1,
+ * cin % 8, cout % 8 or a channel offset / stride that is no multiple of 8. The descriptor is judged
+ * before the data pointers, as in ycx_conv2d_grouped. */
+ycx_status ycx_deconv2d(const ycx_conv_desc* d, const void* x, const void* w, const float* bias, void* y,
+                        void* stream);
 /* ycx_conv2d with a caller-owned workspace for d->k_split > 1 (split-K: fp32 partials of
  * every K range, then one reduce launch; ycx_conv2d itself returns YCX_ERR_CAPACITY for
  * k_split > 1). ycx_conv_workspace_size: the bytes it needs (0 without a split). */

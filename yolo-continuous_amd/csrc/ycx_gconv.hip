@@ -17,6 +17,17 @@
 //     one fmaf each, so the fp32 parity mode is reproducible run to run.
 //   * epilogue act(acc + bias) (+ residual), converted with the hardware's
 //     round-to-nearest-even casts and written as 16-byte vector stores.
+//
+// Depthwise only (cin_g == 1): also k = 11 and stride 4 or 8, RobustConv2's strided half
+// (nets/common.py:128-132: [32, 5, 2], [32, 7, 4], [32, 11, 8]). The staged patch of a T x T output
+// tile is ((T - 1) s + k)^2 pixels of 32 channels, and the 48 KB patch buffer holds 768 pixels of
+// 16-bit data, 384 of fp32: at s = 8, k = 11 the smallest tile the s <= 2 table offers (1 x 8:
+// 11 x 67 pixels) fits 16-bit only, and its square tiles are far out of reach (8 x 8: 67 x 67). So
+// strides 4 and 8 pick from a table of their own, 8 x 4 down to 1 x 1 outputs: at s = 4, k = 7 that
+// is 8 x 4 (35 x 19) in 16-bit and 4 x 4 (19 x 19) in fp32, at s = 8, k = 11 it is 4 x 2 (35 x 19)
+// and 2 x 2 (19 x 19). The windows of such a conv barely overlap (3 pixels of 11 at s = 8), so a small
+// tile costs little halo: 35 x 19 staged for 32 x 16 used. Every (k, s, g) with s <= 2 keeps its table,
+// its tile and its instantiation.
 #include "ycx_internal.h"
 
 namespace {
@@ -230,6 +241,9 @@ ycx_status launch_k(const GArgs& a, int k, int g, unsigned nwg, hipStream_t st) 
     case 3: return launch_g<T, 3>(a, g, nwg, st);
     case 5: return launch_g<T, 5>(a, g, nwg, st);
     case 7: return launch_g<T, 7>(a, g, nwg, st);
+    case 11:  // depthwise only (validated by the caller)
+      hipLaunchKernelGGL((gconv_kernel<T, 11, 1>), dim3(nwg), dim3(256), 0, st, a);
+      return ycx_launch_status();
     default: return YCX_ERR_UNSUPPORTED;
   }
 }
@@ -238,7 +252,7 @@ ycx_status launch_k(const GArgs& a, int k, int g, unsigned nwg, hipStream_t st) 
 
 extern "C" ycx_status ycx_conv2d_grouped(const ycx_conv_desc* d, const void* x, const float* w, const float* bias,
                                          void* y, const void* residual, void* stream) {
-  YCX_CHECK_ARG(d && x && w && bias && y);
+  YCX_CHECK_ARG(d);  // the descriptor is judged before the data pointers (checked below, before the launch)
   YCX_CHECK_ARG(d->n > 0 && d->h > 0 && d->w > 0 && d->cin > 0 && d->cout > 0 && d->ho > 0 && d->wo > 0);
   YCX_CHECK_ARG(d->kh > 0 && d->kw > 0 && d->stride > 0 && d->pad >= 0 && d->groups > 0);
   YCX_CHECK_ARG(d->cin % d->groups == 0 && d->cout % d->groups == 0);
@@ -249,8 +263,9 @@ extern "C" ycx_status ycx_conv2d_grouped(const ycx_conv_desc* d, const void* x, 
   YCX_CHECK_ARG(!residual || (d->res_c_off >= 0 && d->res_c_off + d->cout <= d->res_c_stride));
   const int g = d->cin / d->groups;
   YCX_CHECK_SUPPORTED(d->groups > 1 && g == d->cout / d->groups && (g == 1 || g == 2 || g == 4 || g == 8 || g == 16));
-  YCX_CHECK_SUPPORTED(d->kh == d->kw && (d->kh == 3 || d->kh == 5 || d->kh == 7) && d->pad == d->kh / 2);
-  YCX_CHECK_SUPPORTED(d->stride == 1 || d->stride == 2);
+  YCX_CHECK_SUPPORTED(d->kh == d->kw && (d->kh == 3 || d->kh == 5 || d->kh == 7 || (g == 1 && d->kh == 11)) &&
+                      d->pad == d->kh / 2);
+  YCX_CHECK_SUPPORTED(d->stride == 1 || d->stride == 2 || (g == 1 && (d->stride == 4 || d->stride == 8)));
   YCX_CHECK_SUPPORTED(d->dtype == YCX_DT_BF16 || d->dtype == YCX_DT_F16 || d->dtype == YCX_DT_F32);
   YCX_CHECK_SUPPORTED(d->act == YCX_ACT_NONE || d->act == YCX_ACT_SILU || d->act == YCX_ACT_LEAKY);
   YCX_CHECK_SUPPORTED(d->out_layout == YCX_OUT_NHWC && !d->in_pool && d->k_split <= 1);
@@ -259,15 +274,18 @@ extern "C" ycx_status ycx_conv2d_grouped(const ycx_conv_desc* d, const void* x, 
                       d->out_c_stride % 8 == 0);
   if (residual) YCX_CHECK_SUPPORTED(d->res_c_off % 8 == 0 && d->res_c_stride % 8 == 0);
   YCX_CHECK_SUPPORTED((long long)d->n * d->h * d->w < (1LL << 31) && (long long)d->n * d->ho * d->wo < (1LL << 31));
+  YCX_CHECK_ARG(x && w && bias && y);
 
   const int k = d->kh, s = d->stride, esz = d->dtype == YCX_DT_F32 ? 4 : 2;
   // Among the tiles whose input patch fits the LDS budget, the one that spends the fewest
   // pixel slots on this map (a workgroup runs its 64 pixel lanes once per 64 tile pixels);
   // ties go to the larger tile (less halo).
-  static const int tiles[][2] = {{16, 4}, {8, 4}, {16, 3}, {8, 3}, {4, 4}, {4, 3}, {2, 3}, {1, 3}};  // th, log2(tw)
+  static const int tiles[8][2] = {{16, 4}, {8, 4}, {16, 3}, {8, 3}, {4, 4}, {4, 3}, {2, 3}, {1, 3}};  // th, log2(tw)
+  // strides 4 and 8 (depthwise): the patch grows with s, so smaller tiles (file header)
+  static const int wide[8][2] = {{8, 2}, {4, 3}, {4, 2}, {4, 1}, {2, 2}, {2, 1}, {1, 1}, {1, 0}};
   int th = 0, twl = 0, ih = 0, iw = 0;
   long long best = -1;
-  for (const auto& t : tiles) {
+  for (const auto& t : s > 2 ? wide : tiles) {
     const int tih = (t[0] - 1) * s + k, tiw = ((1 << t[1]) - 1) * s + k;
     if ((long long)tih * tiw * kChunk * esz > kXBytes) continue;
     const long long ntile = (long long)((d->ho + t[0] - 1) / t[0]) * ((d->wo + (1 << t[1]) - 1) >> t[1]);

@@ -7,7 +7,8 @@ Lowering (once per input shape / device / precision):
    each module into graph nodes — conv (BN folded, RepConv re-parameterised,
    Bottleneck residual fused into the epilogue), stem conv (first conv on the
    fp32 NCHW image; ``stem_reorg`` when ReOrg precedes it: the space-to-depth is folded into
-   that conv's operand gather), max-pool, upsample, concat, Detect/IDetect heads.
+   that conv's operand gather), grouped conv, transposed conv (kernel == stride: ``deconv``), max-pool,
+   upsample, concat, Detect/IDetect heads.
 2. Passes: nearest-x2 upsample fused into its producing conv's store
    (YCX_OUT_NHWC_UP2); the SPPCSPC 5/9/13 pools run as a k5 cascade (exact for
    max with -inf padding); every concat input that a kernel produces is written
@@ -32,7 +33,7 @@ from torch import nn
 
 from . import _lib as L
 from .nets.common import (SP, SPP, SPPCSPC, SPPF, MP, Bottleneck, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC,
-                          Concat, Conv, DownC, ReOrg, RepConv, Res, RobustConv)
+                          Concat, Conv, DownC, ReOrg, RepConv, Res, RobustConv, RobustConv2)
 from .nets.detect import Detect, IAuxDetect, IDetect
 from .schedule import Schedule, cascade_fits, cout_pad  # noqa: F401  (cascade_fits: re-exported)
 
@@ -114,9 +115,13 @@ def act_of(mod):
     raise NotImplementedError(f"ycx: activation {type(mod).__name__} has no HIP epilogue")
 
 
-# what ycx_conv2d_grouped takes (include/ycx.h): channels per group (cin_g == cout_g) and kernel sizes
+# what ycx_conv2d_grouped takes (include/ycx.h): channels per group (cin_g == cout_g), kernel sizes and strides;
+# k 11 and strides 4, 8 for a depthwise conv (cin_g 1) only
 GCONV_CIN_G = (1, 2, 4, 8, 16)
-GCONV_K = (3, 5, 7)
+GCONV_K = (3, 5, 7, 11)
+GCONV_S = (1, 2, 4, 8)
+# what ycx_deconv2d takes: kernel == stride
+DECONV_S = (2, 4, 8)
 
 
 class Graph:
@@ -163,16 +168,34 @@ class Graph:
         if cin_g * groups != x.c or cout % groups:
             raise NotImplementedError(f"ycx: grouped/mismatched conv (cin {cin_g} x {groups} groups vs input {x.c})")
         cout_g = cout // groups
-        if not (cin_g == cout_g and cin_g in GCONV_CIN_G and k in GCONV_K and p == k // 2 and s in (1, 2)
-                and cout % 8 == 0 and not head):
+        wide = k == 11 or s in (4, 8)  # the depthwise-only shapes
+        if not (cin_g == cout_g and cin_g in GCONV_CIN_G and k in GCONV_K and p == k // 2 and s in GCONV_S
+                and (cin_g == 1 or not wide) and cout % 8 == 0 and not head):
             raise NotImplementedError(
                 f"ycx: grouped conv with cin_g {cin_g}, cout_g {cout_g}, k {k} (s {s}, p {p}, cout {cout}) has no HIP "
                 f"kernel: ycx_conv2d_grouped takes cin_g == cout_g in {GCONV_CIN_G}, k in {GCONV_K}, p == k // 2, "
-                f"s 1 or 2, cout % 8 == 0")
+                f"s in {GCONV_S} (k 11 and s 4, 8: depthwise only), cout % 8 == 0")
         ho, wo = (x.h + 2 * p - k) // s + 1, (x.w + 2 * p - k) // s + 1
         ins = [x] + ([residual] if residual is not None else [])
         return self.add('gconv', ins, Val(x.n, ho, wo, cout), w=w64, b=b64, k=k, s=s, p=p, act=act[0], slope=act[1],
                         residual=residual, ho=ho, wo=wo, layout=L.OUT_NHWC, groups=groups)
+
+    def deconv(self, x: Val, w64, b64, s, act=(L.ACT_NONE, 0.0)):
+        """A transposed conv with kernel == stride == s (weights [cin][cout][s][s], torch's layout) as a
+        node of its own kind, 'deconv' (ycx_deconv2d): like 'gconv', no conv-fusing pass looks at it;
+        only the concat-slice aliasing takes it."""
+        cin, cout = int(w64.shape[0]), int(w64.shape[1])
+        if x.role in ('input', 'reorg'):
+            raise NotImplementedError("ycx: transposed conv on the model input")
+        if tuple(w64.shape[2:]) != (s, s) or s not in DECONV_S:
+            raise NotImplementedError(f"ycx: transposed conv with kernel {tuple(w64.shape[2:])}, stride {s} has no HIP "
+                                      f"kernel: ycx_deconv2d takes kernel_size == stride in {DECONV_S}")
+        if cin != x.c or cin % 8 or cout % 8:
+            raise NotImplementedError(f"ycx: transposed conv with cin {cin} (input {x.c}), cout {cout}: ycx_deconv2d "
+                                      f"takes cin == the input's channels, cin % 8 == 0, cout % 8 == 0")
+        ho, wo = x.h * s, x.w * s
+        return self.add('deconv', [x], Val(x.n, ho, wo, cout), w=w64, b=b64, k=s, s=s, p=0, act=act[0], slope=act[1],
+                        residual=None, ho=ho, wo=wo, layout=L.OUT_NHWC)
 
     def pool(self, x: Val, k, s, p):
         if x.role == 'input':
@@ -222,8 +245,42 @@ def fold_robustconv(m: RobustConv):
     return w, b
 
 
+def fold_robustconv2(m: RobustConv2):
+    """RobustConv2's biased transposed conv with its layer scale folded in, float64 (W [cin][cout][s][s], b):
+    (W^T x + b) * gamma = (gamma W)^T x + gamma b, gamma along W's second dim (nets/common.py:138-139)."""
+    c = m.conv_deconv
+    w = c.weight.detach().to('cpu', torch.float64)
+    b = c.bias.detach().to('cpu', torch.float64)
+    if m.gamma is not None:
+        gm = m.gamma.detach().to('cpu', torch.float64)
+        w, b = w * gm.reshape(1, -1, 1, 1), b * gm
+    return w, b
+
+
+def deconv_module(g: 'Graph', c: nn.ConvTranspose2d, x, w=None, b=None):
+    """An nn.ConvTranspose2d (its own weights, or the folded w, b given) as a 'deconv' node; every form
+    ycx_deconv2d does not take is refused by the name of the offending field."""
+    k, s = _square(c.kernel_size, 'kernel_size'), _square(c.stride, 'stride')
+    for field, ok in (('kernel_size', k == s), ('padding', _pair(c.padding) == (0, 0)),
+                      ('output_padding', _pair(c.output_padding) == (0, 0)), ('dilation', _pair(c.dilation) == (1, 1)),
+                      ('groups', c.groups == 1), ('stride', s in DECONV_S)):
+        if not ok:
+            raise NotImplementedError(
+                f"ycx: nn.ConvTranspose2d with {field} {getattr(c, field)} (kernel_size {k}, stride {s}) has no HIP "
+                f"kernel: ycx_deconv2d takes kernel_size == stride in {DECONV_S}, padding 0, output_padding 0, "
+                f"dilation 1, groups 1")
+    if w is None:
+        w = c.weight.detach().to('cpu', torch.float64)
+        b = c.bias.detach().to('cpu', torch.float64) if c.bias is not None else torch.zeros(w.shape[1],
+                                                                                            dtype=torch.float64)
+    return g.deconv(x, w, b, s)
+
+
 def check_plan_precision(plan, precision):
     """What a plan cannot run in a given precision, raised before anything is allocated."""
+    if precision == 'fp8' and any(nd.kind == 'deconv' for nd in plan.graph.nodes):
+        raise NotImplementedError("ycx: transposed conv has no fp8 path (ycx_deconv2d takes bf16, fp16 and f32); "
+                                  "run this model in 'fp16', 'bf16' or 'f32'")
     if precision == 'fp8' and any(nd.kind == 'gconv' for nd in plan.graph.nodes):
         raise NotImplementedError("ycx: grouped conv has no fp8 path (ycx_conv2d_grouped takes bf16, fp16 and f32); "
                                   "run this model in 'fp16', 'bf16' or 'f32'")
@@ -301,6 +358,11 @@ def lower_module(g: Graph, m, x):
     if isinstance(m, RobustConv):  # nets/common.py:121-124; its channels_last call changes no value
         w, b = fold_robustconv(m)
         return g.conv(conv_module(g, m.conv_dw, x), w, b, 1, 1, 0)
+    if isinstance(m, RobustConv2):  # nets/common.py:137-139
+        w, b = fold_robustconv2(m)
+        return deconv_module(g, m.conv_deconv, conv_module(g, m.conv_strided, x), w, b)
+    if isinstance(m, nn.ConvTranspose2d):
+        return deconv_module(g, m, x)
     if isinstance(m, SPPCSPC):
         x1 = conv_module(g, m.cv4, conv_module(g, m.cv3, conv_module(g, m.cv1, x)))
         y1 = conv_module(g, m.cv6, conv_module(g, m.cv5, g.concat([x1] + pyramid(g, x1, list(m.m)))))
@@ -394,9 +456,13 @@ class Plan:
     @property
     def conv_flops(self):
         """Algorithmic FLOPs: sum of 2*N*Ho*Wo*Cout*Cin*k*k over the folded convs (a grouped conv:
-        Cin = cin_g, the second dim of its weights)."""
+        Cin = cin_g, the second dim of its weights), plus 2*N*H*W*Cin*s*s*Cout over the transposed convs
+        (each input pixel feeds an s x s block; weights [cin][cout][s][s])."""
+        nodes = self.graph.nodes
         return sum(2 * nd.inputs[0].n * nd.p['ho'] * nd.p['wo'] * int(nd.p['w'].shape[0]) * int(nd.p['w'].shape[1])
-                   * nd.p['k'] ** 2 for nd in self.graph.nodes if nd.kind in ('conv', 'stem', 'stem_reorg', 'gconv'))
+                   * nd.p['k'] ** 2 for nd in nodes if nd.kind in ('conv', 'stem', 'stem_reorg', 'gconv')) + \
+            sum(2 * nd.inputs[0].n * nd.inputs[0].h * nd.inputs[0].w * int(nd.p['w'].shape[0]) * nd.p['s'] ** 2
+                * int(nd.p['w'].shape[1]) for nd in nodes if nd.kind == 'deconv')
 
     def counts(self):
         """Node kinds after the passes; 'conv' counts the original convs (a merged
@@ -456,7 +522,7 @@ class Plan:
             copies, off = [], 0
             for v in node.inputs:
                 if v.buf is None and v.role == 'act' and v.producer is not None and \
-                        v.producer.kind in ('conv', 'stem', 'stem_reorg', 'gconv', 'pool', 'up'):
+                        v.producer.kind in ('conv', 'stem', 'stem_reorg', 'gconv', 'deconv', 'pool', 'up'):
                     v.buf, v.coff = out.buf, off
                 else:
                     copies.append((v, off))
@@ -529,6 +595,13 @@ def pack_fp8_weights(wp):
     out = torch.zeros((cpad, ktp), dtype=torch.float32)
     out[:, :kt] = rows.to(torch.float32)
     return out.clamp(-448.0, 448.0).to(torch.float8_e4m3fn), sw
+
+
+def pack_deconv_weights(w64, dtype):
+    """float64 [cin][cout][s][s] (torch's ConvTranspose2d layout) -> [s*s][cout][cin] in ``dtype``: the rows
+    of ycx_deconv2d's GEMM, tap-major (tap = dy * s + dx), K = cin contiguous (include/ycx.h)."""
+    cin, cout, s = int(w64.shape[0]), int(w64.shape[1]), int(w64.shape[2])
+    return w64.permute(2, 3, 1, 0).reshape(s * s, cout, cin).contiguous().to(dtype)
 
 
 class Engine:
@@ -633,7 +706,7 @@ class Engine:
         # size and the A/B switches, and a prepack file is reused at any batch size
         self.packed = {}
         self._conv_index = {id(nd): i for i, nd in enumerate(
-            nd for nd in self.graph.nodes if nd.kind in ('conv', 'stem', 'stem_reorg', 'gconv'))}
+            nd for nd in self.graph.nodes if nd.kind in ('conv', 'stem', 'stem_reorg', 'gconv', 'deconv'))}
         for b in self.schedule.activation_bufs:
             b.tensor = torch.empty((b.n, b.h, b.w, b.c), dtype=dt, device=dev)
             self.buffers.append(b.tensor)
@@ -644,6 +717,7 @@ class Engine:
                 'conv_pair': lambda la: self._pair_op(*la.nodes, store_a=la.store_a),
                 'conv': lambda la: self._conv_op(*la.nodes),
                 'gconv': lambda la: self._gconv_op(*la.nodes),
+                'deconv': lambda la: self._deconv_op(*la.nodes),
                 'pool': lambda la: self._pool_op(la.nodes[0], levels=la.levels),
                 'copy': lambda la: self._copy_op(la.src, la.dst, la.off, la.scale, nchw=la.nchw)}
         ops = [emit[la.kind](la) for la in self.schedule.launches]
@@ -830,6 +904,43 @@ class Engine:
         self.op_info.append(dict(kind='gconv', name=f"gconv_g{cin_g}_k{k}s{p['s']}", flops=flops,
                                  shape=(x.n, x.h, x.w, x.c, cout, k, p['s']), parts=1, bytes=nbytes,
                                  out_bytes=nbytes - self._conv_bytes(d, wt, residual=r is not None, out_bytes=False)))
+        return op
+
+    def _deconv_op(self, node):
+        """One OP_DECONV (ycx_deconv2d): weights [s*s][cout][cin] in the activation dtype, fp32 bias [cout],
+        unscaled (plain YCX_ACT_* epilogues)."""
+        p, x, out = node.p, node.inputs[0], node.out
+        cin, cout, s = int(p['w'].shape[0]), int(p['w'].shape[1]), p['s']
+        wshape, bshape = (s * s, cout, cin), (cout,)
+        i = 2 * self._conv_index[id(node)]
+        if self.prepacked is not None:
+            wt, bt = self.prepacked.get(f"p{i}"), self.prepacked.get(f"p{i + 1}")
+            if wt is None or bt is None or tuple(wt.shape) != wshape or wt.dtype != self.dtype or \
+                    tuple(bt.shape) != bshape or bt.dtype != torch.float32:
+                raise ValueError(f"ycx: prepacked weights do not match this plan at tensor p{i}")
+        else:
+            wt, bt = pack_deconv_weights(p['w'], self.dtype), p['b'].to(torch.float32)
+        wt, bt = wt.to(self.device), bt.to(self.device)
+        self.params += [wt, bt]
+        self.packed[f"p{i}"], self.packed[f"p{i + 1}"] = wt, bt
+        d = L.ConvDesc()
+        d.n, d.h, d.w, d.cin, d.in_c_off, d.in_c_stride = x.n, x.h, x.w, cin, x.coff, x.buf.c
+        d.ho, d.wo, d.cout, d.cout_pad, d.out_c_off, d.out_c_stride = p['ho'], p['wo'], cout, cout, out.coff, out.buf.c
+        d.kh = d.kw = d.stride = s
+        d.pad, d.act, d.leaky_slope = 0, p['act'], p['slope']
+        d.dtype, d.out_layout = self.dt, L.OUT_NHWC
+        d.out_scale = d.res_scale = 1.0
+        flops = 2 * x.n * x.h * x.w * cin * s * s * cout
+        self.conv_flops += flops
+        op = L.Op()
+        op.kind = L.OP_DECONV
+        op.d.conv = d
+        op.in_ = x.buf.tensor.data_ptr()
+        op.weight, op.bias = wt.data_ptr(), bt.data_ptr()
+        op.out = out.buf.tensor.data_ptr()
+        nbytes = self._conv_bytes(d, wt)
+        self.op_info.append(dict(kind='deconv', name=f"deconv_s{s}", flops=flops, shape=(x.n, x.h, x.w, cin, cout, s, s),
+                                 parts=1, bytes=nbytes, out_bytes=nbytes - self._conv_bytes(d, wt, out_bytes=False)))
         return op
 
     def _conv_bytes(self, d, wt, stem=False, pooled=False, residual=False, out_bytes=True):
@@ -1054,10 +1165,10 @@ class Engine:
             if v:
                 setattr(o, field, v + i0 * per_image)
 
-        if o.kind in (L.OP_CONV, L.OP_STEM, L.OP_STEM2, L.OP_STEM_REORG, L.OP_GCONV):
+        if o.kind in (L.OP_CONV, L.OP_STEM, L.OP_STEM2, L.OP_STEM_REORG, L.OP_GCONV, L.OP_DECONV):
             d = o.d.pair[1] if o.kind == L.OP_STEM2 else o.d.conv
             first = o.d.pair[0] if o.kind == L.OP_STEM2 else d
-            if o.kind in (L.OP_CONV, L.OP_GCONV):
+            if o.kind in (L.OP_CONV, L.OP_GCONV, L.OP_DECONV):
                 shift('in_', (4 if d.in_pool else 1) * d.h * d.w * d.in_c_stride * es)
             else:  # fp32 NCHW image
                 shift('in_', first.cin * first.h * first.w * 4)
@@ -1087,7 +1198,7 @@ class Engine:
 
     @staticmethod
     def _op_out_h(op):
-        if op.kind in (L.OP_CONV, L.OP_STEM, L.OP_HEAD, L.OP_STEM_REORG, L.OP_GCONV):
+        if op.kind in (L.OP_CONV, L.OP_STEM, L.OP_HEAD, L.OP_STEM_REORG, L.OP_GCONV, L.OP_DECONV):
             return op.d.conv.ho
         if op.kind == L.OP_STEM2:
             return op.d.pair[1].ho

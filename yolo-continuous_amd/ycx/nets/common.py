@@ -58,6 +58,20 @@ class RobustConv(_Holder):
         self.gamma = nn.Parameter(layer_scale_init_value * torch.ones(c2)) if layer_scale_init_value > 0 else None
 
 
+class RobustConv2(_Holder):
+    """conv_deconv(conv_strided(x)) * gamma: a depthwise k x k Conv of stride s, a biased transposed
+    conv with kernel == stride == s that restores the resolution, and a learned per-channel layer scale
+    (nets/common.py:127-139; its comment recommends [32, 5, 2], [32, 7, 4] or [32, 11, 8]). The engine
+    folds gamma into the transposed conv (ycx_deconv2d)."""
+
+    def __init__(self, c1, c2, k=7, s=4, p=None, g=1, act=True, layer_scale_init_value=1e-6):
+        super().__init__()
+        self.conv_strided = Conv(c1, c1, k=k, s=s, p=p, g=c1, act=act)
+        self.conv_deconv = nn.ConvTranspose2d(in_channels=c1, out_channels=c2, kernel_size=s, stride=s, padding=0,
+                                              bias=True, dilation=1, groups=1)
+        self.gamma = nn.Parameter(layer_scale_init_value * torch.ones(c2)) if layer_scale_init_value > 0 else None
+
+
 class MP(_Holder):
     """MaxPool2d(k, k) (nets/common.py:25-31)."""
 

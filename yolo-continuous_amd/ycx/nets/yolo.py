@@ -27,7 +27,7 @@ from torch import nn
 from ..utils.helper_io import cvt_cfg
 from .common import (SP, SPP, SPPCSPC, SPPF, MP, Bottleneck, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC,
                      Concat, Conv, DownC, ImplicitA, ImplicitM, ReOrg, RepConv, Res, ResCSPA, ResCSPB, ResCSPC, ResX,
-                     ResXCSPA, ResXCSPB, ResXCSPC, RobustConv, dw_conv)
+                     ResXCSPA, ResXCSPB, ResXCSPC, RobustConv, RobustConv2, dw_conv)
 from .detect import Detect, IAuxDetect, IDetect
 
 
@@ -42,21 +42,23 @@ _MODULES = {
     'ImplicitM': ImplicitM, 'Detect': Detect, 'IDetect': IDetect, 'IAuxDetect': IAuxDetect,
     'nn.Conv2d': nn.Conv2d, 'nn.BatchNorm2d': nn.BatchNorm2d, 'nn.Upsample': nn.Upsample,
     'ReOrg': ReOrg, 'DownC': DownC,
-    'dw_conv': dw_conv, 'RobustConv': RobustConv, 'Res': Res, 'ResX': ResX,
+    'dw_conv': dw_conv, 'RobustConv': RobustConv, 'RobustConv2': RobustConv2, 'Res': Res, 'ResX': ResX,
+    'nn.ConvTranspose2d': nn.ConvTranspose2d,
     'ResCSPA': ResCSPA, 'ResCSPB': ResCSPB, 'ResCSPC': ResCSPC,
     'ResXCSPA': ResXCSPA, 'ResXCSPB': ResXCSPB, 'ResXCSPC': ResXCSPC,
 }
 # Reference modules constructible by its parse_model but used by neither shipped
 # YAML: named here so the error says "out of scope", not "unknown".
 _OUT_OF_SCOPE = {
-    'Chuncat', 'Shortcut', 'Foldcut', 'RobustConv2', 'GhostConv', 'Stem',
+    'Chuncat', 'Shortcut', 'Foldcut', 'GhostConv', 'Stem',
     'Ghost', 'GhostSPPCSPC', 'GhostStem', 'Focus', 'Contract', 'Expand', 'Classify',
     'TransformerLayer', 'TransformerBlock', 'IBin', 'RepBottleneck',
 } | {f'{p}{s}' for p in ('RepRes', 'RepResX', 'Ghost', 'RepBottleneck')
      for s in ('CSPA', 'CSPB', 'CSPC')}
 
-_CONV_LIKE = (nn.Conv2d, Conv, RobustConv, dw_conv, RepConv, DownC, SPP, SPPF, SPPCSPC, Bottleneck, BottleneckCSPA,
-              BottleneckCSPB, BottleneckCSPC, Res, ResCSPA, ResCSPB, ResCSPC, ResX, ResXCSPA, ResXCSPB, ResXCSPC)
+_CONV_LIKE = (nn.Conv2d, Conv, RobustConv, RobustConv2, dw_conv, RepConv, DownC, SPP, SPPF, SPPCSPC, Bottleneck,
+              BottleneckCSPA, BottleneckCSPB, BottleneckCSPC, Res, ResCSPA, ResCSPB, ResCSPC, ResX, ResXCSPA, ResXCSPB,
+              ResXCSPC)
 _CSP_LIKE = (DownC, SPPCSPC, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC, ResCSPA, ResCSPB, ResCSPC, ResXCSPA,
              ResXCSPB, ResXCSPC)
 _ACTS = {'LeakyReLU': nn.LeakyReLU, 'SiLU': nn.SiLU, 'Identity': nn.Identity}

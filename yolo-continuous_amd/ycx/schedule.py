@@ -26,6 +26,7 @@ class Launch:
                ``store_a``: a's map is written
     conv       nodes (conv,) or (conv, pool), the pool folded into the conv (kinds conv, stem, stem_reorg)
     gconv      nodes (gconv,)
+    deconv     nodes (deconv,)
     pool       nodes: the cascade's pools, ``levels`` of them
     copy       nodes (up | concat | tonchw,): ``src`` -> channels from ``off`` of ``dst``, upsampled
                by ``scale`` (1 or 2), ``nchw``: to the fp32 NCHW output
@@ -248,8 +249,8 @@ class Schedule:
                 add('conv_pair', nd, pairs[i], *trio, store_a=len(nd.out.consumers) > 1 and not trio)
             elif k in ('conv', 'stem', 'stem_reorg'):
                 add('conv', nd, *([pooled[i]] if i in pooled else []))
-            elif k == 'gconv':
-                add('gconv', nd)
+            elif k in ('gconv', 'deconv'):
+                add(k, nd)
             elif k == 'pool':
                 chain = cascades.get(i, [nd])
                 add('pool', *chain, levels=len(chain))
