@@ -94,7 +94,20 @@ enum {
  * epilogue computes act(acc * dq + bias) (+ residual * res_scale) and stores
  * e4m3(clamp(v * out_scale)) (fp32 NCHW head outputs: unscaled). The stem
  * (ycx_stem_conv) reads the fp32 image with fp32 weights and only its output
- * is e4m3 (out_scale). cout_pad % 64 == 0 and cin in {32, 64, 128k}. */
+ * is e4m3 (out_scale). cout_pad % 64 == 0 and cin in {32, 64, 128k}.
+ * Channel slices: x, y and the residual are slices of wider buffers, in_c_off + cin <= in_c_stride,
+ * out_c_off + cout <= out_c_stride (YCX_OUT_NCHW_F32: out_c_off is the first of cout planes), and the
+ * residual's res_c_off + cout <= res_c_stride. 16-byte channel vectors: in_c_off and in_c_stride are
+ * multiples of 8 (16-bit), 4 (f32) or 16 (fp8); for the NHWC layouts cout, out_c_off and out_c_stride
+ * are multiples of 8, as are res_c_off and res_c_stride; YCX_OUT_NCHW_F32 has no such rule (cout 255).
+ * cin is a multiple of the tile's K step, so no entry point reads a channel outside
+ * [in_c_off, in_c_off + cin), nor a pixel outside the tensor: whatever lies there, NaN included,
+ * never reaches an output.
+ * Padded output channels: rows cout .. cout_pad of w and entries cout .. cout_pad of bias may hold any
+ * finite values, not only zeros (the zero padding promised above is the fp8 rows' K padding alone).
+ * They are computed and never stored: no entry point writes outside [out_c_off, out_c_off + cout) of
+ * a pixel (of the planes, for YCX_OUT_NCHW_F32). tests/test_gpu_conv_exact.py holds every dense kernel
+ * to both rules with NaN around the inputs, sentinels around the outputs and live padding rows. */
 typedef struct ycx_conv_desc {
   int32_t n, h, w, cin, in_c_off, in_c_stride;
   int32_t ho, wo, cout, cout_pad, out_c_off, out_c_stride;

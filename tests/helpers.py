@@ -330,3 +330,118 @@ def rounding_stats(t64, dtype):
     inexact = lo != hi
     tie = inexact & ((t64 - lo) == (hi - t64))
     return float(inexact.double().mean()), float(tie.double().mean())
+
+
+# ---- the frame of the exact files (test_gpu_conv_exact.py, trio_case.py, test_gpu_stem_reorg.py) ----
+# Outputs: the channel slice lies in the interior of a buffer pre-filled with a sentinel, and the whole
+# buffer is compared, so a store before or after the slice, and an element left unwritten, show.
+# Inputs: the channel slice lies between NaN channels and the tensor between NaN guards inside one
+# allocation, so a read outside the operands reaches the output as NaN instead of as whatever the
+# allocator left there. Padding weight rows and bias entries (cout .. cout_pad) hold grid values, so
+# a padding channel that is stored lands as a value, not as the 0 a zero row computes.
+SENTINEL = 3.0             # NHWC outputs: every element type represents it
+SENTINEL_F32 = -6.0e23     # fp32 NCHW outputs: no reference comes near it
+OUT_LEAD, OUT_TAIL = 16, 8  # NHWC output slice at channel 16 of a buffer 16 + cout + 8 wide
+IN_LEAD, IN_TAIL = 8, 8     # input (and residual) slice at channel 8 of a buffer 8 + c + 8 wide
+MIN_LIVE_PADDING = 0.90
+
+
+def assert_bits(got, exp, what=""):
+    """torch.equal on the bit patterns of two whole buffers; on a mismatch, how many elements and how far."""
+    it = _ELT_INT[got.dtype]
+    assert got.shape == exp.shape and got.dtype == exp.dtype, (got.shape, exp.shape, got.dtype, exp.dtype)
+    gb, eb = got.contiguous().view(it), exp.contiguous().view(it)
+    if torch.equal(gb, eb):
+        return
+    bad = gb != eb
+    d = elt_ulps(got, exp, got.dtype)[bad]
+    raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements differ from RNE(true sum) or the "
+                         f"sentinel; distance in representable values: min {int(d.min())}, max {int(d.max())}; "
+                         f"{int(got.isnan().sum())} NaN; first at {[int(v) for v in bad.nonzero()[0]]}")
+
+
+def out_frame(n, ho, wo, cout, dtype, lead=OUT_LEAD, tail=OUT_TAIL):
+    """A sentinel-filled NHWC output buffer [n][ho][wo][lead + cout + tail]; the slice starts at ``lead``."""
+    assert lead >= 0 and tail > 0
+    return torch.full((n, ho, wo, lead + cout + tail), SENTINEL, dtype=dtype)
+
+
+def expected_frame(elems_nhwc, lead=OUT_LEAD, tail=OUT_TAIL):
+    """The whole expected buffer of out_frame: ``elems_nhwc`` (element type) in the slice, the sentinel outside."""
+    n, ho, wo, c = elems_nhwc.shape
+    exp = out_frame(n, ho, wo, c, elems_nhwc.dtype, lead, tail)
+    exp[..., lead:lead + c] = elems_nhwc
+    return exp
+
+
+def out_planes(n, cout, ho, wo):
+    """A sentinel-filled fp32 NCHW output buffer [n][cout + 2][ho][wo]: out_c_off 1, out_c_stride cout + 2."""
+    return torch.full((n, cout + 2, ho, wo), SENTINEL_F32, dtype=torch.float32)
+
+
+def expected_planes(ref_nchw):
+    """The whole expected buffer of out_planes for an fp32 reference [n][cout][ho][wo]."""
+    assert ref_nchw.dtype == torch.float32 and not bool((ref_nchw == SENTINEL_F32).any())
+    n, c, ho, wo = ref_nchw.shape
+    exp = out_planes(n, c, ho, wo)
+    exp[:, 1:1 + c] = ref_nchw
+    return exp
+
+
+def nan_frame(t_nhwc, lead=IN_LEAD, tail=IN_TAIL):
+    """[..., lead + c + tail] with ``t_nhwc`` at channel ``lead`` and NaN in every other channel."""
+    c = t_nhwc.shape[-1]
+    full = torch.full((*t_nhwc.shape[:-1], lead + c + tail), float('nan'), dtype=t_nhwc.dtype)
+    full[..., lead:lead + c] = t_nhwc
+    return full
+
+
+def guard_elems(pad, w, row_elems, itemsize, align_bytes=16):
+    """Elements of one NaN guard: at least (pad * w + pad + 1) * row_elems -- every position a tap of a
+    pad-wide border can name before the first or after the last element, plus one -- rounded up so that
+    the tensor behind it keeps ``align_bytes``. row_elems: in_c_stride (NHWC) or 1 (an NCHW image)."""
+    a = align_bytes // itemsize
+    return -(-((pad * w + pad + 1) * row_elems) // a) * a
+
+
+def guarded(t, guard, device, fill=float('nan'), align_bytes=16):
+    """``t`` (CPU, its final dtype) on ``device`` in the middle of ONE flat allocation, with ``guard``
+    elements of ``fill`` (NaN for an input) before and after it. The guards are inside the allocation:
+    nothing can fault, a read outside the tensor just becomes deterministic. Returns the view (it keeps
+    the allocation alive)."""
+    assert guard > 0 and (guard * t.element_size()) % align_bytes == 0
+    flat = torch.full((2 * guard + t.numel(),), fill, dtype=t.dtype)
+    flat[guard:guard + t.numel()] = t.reshape(-1)
+    v = flat.to(device)[guard:guard + t.numel()].view(t.shape)
+    assert v.data_ptr() % align_bytes == 0
+    return v
+
+
+OUT_GUARD = 1024  # elements of sentinel before and after an output buffer (a spilled padding channel of the
+                  # last pixel, or a store in front of the first, stays inside the allocation and shows)
+
+
+def guarded_out(t, device, guard=OUT_GUARD):
+    """An output buffer ``t`` (CPU, pre-filled with its sentinel) on ``device`` between two guards of the
+    same sentinel; fetch it with fetch_out, which also checks the guards."""
+    return guarded(t, guard, device, fill=t.reshape(-1)[0].item())
+
+
+def fetch_out(v, sentinel, guard=OUT_GUARD, what=""):
+    """The CPU copy of a guarded_out buffer after the launch; asserts both guards still hold the sentinel."""
+    flat = v._base.cpu()  # the flat allocation guarded() made
+    assert v.storage_offset() == guard and flat.dim() == 1 and flat.numel() == 2 * guard + v.numel()
+    for name, part in (("before", flat[:guard]), ("after", flat[guard + v.numel():])):
+        assert bool((part == sentinel).all()), f"{what}: {int((part != sentinel).sum())} elements written {name} the buffer"
+    return v.cpu()
+
+
+def live_padding_share(pad_elems, sentinel):
+    """Share of what the padding channels would store (``pad_elems``, already in the output's element
+    type) whose bits differ from the sentinel they would land on; asserts >= MIN_LIVE_PADDING."""
+    it = _ELT_INT[pad_elems.dtype]
+    s = torch.full((1,), sentinel, dtype=pad_elems.dtype).view(it)
+    assert pad_elems.numel() > 0
+    share = float((pad_elems.contiguous().view(it) != s).double().mean())
+    assert share >= MIN_LIVE_PADDING, f"padding channels: only {share:.3f} of their values differ from the sentinel"
+    return share

@@ -5,6 +5,16 @@ representable in fp32: the accumulator holds the true sum whatever the tile's K 
 split or MFMA grouping, and the stored element must be RNE(true sum) bit for bit -- no tolerance.
 The reference is torch's float64 conv on the CPU; the element reference is its cast (helpers.rne).
 
+The frame (helpers.py, "the frame of the exact files"): every output is a whole sentinel-filled
+buffer with the channel slice in its interior (NHWC: channel 16 of 16 + cout + 8, a lead of 8 for
+the x2 store and the stems; fp32 NCHW: plane 1 of cout + 2) between two sentinel guards, compared
+bit for bit over the whole buffer; every input slice lies at channel 8 of 8 + cin + 8 channels with
+NaN around it, the residual likewise, and every input tensor (the stems' fp32 images included) lies
+between NaN guards inside one allocation; wherever cout < cout_pad the padding weight rows and bias
+entries hold grid values (the operands' own channels cout .. cout_pad), so a stored padding channel
+is a value and not the 0 of a zero row. tests/test_conv_exact_plan.py walks the case tables below
+without a GPU: span, lossless operands, rounded / tie shares, the live padding, the descriptors.
+
 Grids (helpers.dyadic), chosen per case so that K * max|x|/step_x * max|w|/step_w < 2^20:
   base   x in 1/4 steps within +-4, w in 1/4 steps within +-2, bias in 1/16 steps within +-2
          (bf16 at every K, fp16 at K >= 2304, fp32)
@@ -16,7 +26,7 @@ representable in the element type and >= 1 % are exact ties (conditions on the i
 outputs hold every sum exactly, so there the condition is that the fp32 cast is lossless).
 
 tile -> cases (each in bf16 and fp16; tile 8 in fp32):
-  1-7, 9-18, 24-26, 56   test_exact_general_tiles: n 2, 13 x 11, in_extra 8, out_extra 16,
+  1-7, 9-18, 24-26, 56   test_exact_general_tiles: n 2, 13 x 11,
                          (k, s) in (1,1) (3,1) (3,2) (5,1); act none, leaky 0.125, leaky 0.25
   8                      test_exact_f32_tile8 (the same operands)
   19, 20, 21, 23         test_exact_special_kernels 16 x 16 and 32 x 48
@@ -24,6 +34,7 @@ tile -> cases (each in bf16 and fp16; tile 8 in fp32):
   50                     test_exact_special_kernels 32 x 64 and 31 x 63
   22                     test_exact_special_kernels 13 x 11 (cin 64 / 256) and n 2, 96 x 96
   3, 7, 16, 18, 56, 20, 48   test_exact_epilogue_variants (residual, x2 upsample, fp32 NCHW, cout < cout_pad)
+  16                     test_exact_up2_cout_below_pad (120 of 128 through the x2 store)
   22, 23, 49, 50         test_exact_cout_below_pad
   16, 18, 56             test_exact_splitk (k_split 2, 3, 4; tile 16's chunk-major stride-2 order)
   16                     test_exact_tile16_s2_cin128_chunk_major (unsplit)
@@ -42,11 +53,12 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import dyadic, elt_neighbours, elt_ulps, rne, rounding_stats
+from helpers import (IN_LEAD, IN_TAIL, OUT_LEAD, OUT_TAIL, SENTINEL, SENTINEL_F32, assert_bits, dyadic, elt_neighbours,
+                     elt_ulps, expected_frame, expected_planes, fetch_out, guard_elems, guarded, guarded_out,
+                     live_padding_share, nan_frame, out_frame, out_planes, rne, rounding_stats)
+from ycx import _lib as L  # a missing library is an error, on the CPU too (tests/test_conv_exact_plan.py)
 
-pytestmark = pytest.mark.gpu
-
-L = pytest.importorskip("ycx._lib")
+gpu = pytest.mark.gpu  # every test here; the tables and builders import without a device
 
 TDT = {L.DT_BF16: torch.bfloat16, L.DT_F16: torch.float16, L.DT_F32: torch.float32}
 DT16 = [L.DT_BF16, L.DT_F16]
@@ -55,6 +67,7 @@ MIN_ROUNDED, MIN_TIES = 0.10, 0.01
 ACTS = [(L.ACT_NONE, 0.0), (L.ACT_LEAKY, 0.125), (L.ACT_LEAKY, 0.25)]  # both slopes exact, neither is 0.1
 X_MAX, W_MAX, B_MAX, B_STEP = 4.0, 2.0, 2.0, 1 / 16
 _FP16_GRIDS = [(1 / 16, 1 / 8), (1 / 8, 1 / 8), (1 / 8, 1 / 4), (1 / 4, 1 / 4)]
+UP2_LEAD = STEM_LEAD = 8          # the x2 store and the stems keep their slice at channel 8
 
 
 def pick_grid(K, dtype):
@@ -84,39 +97,30 @@ def check_inputs(ref64, tdt, what=""):
     return rounded, ties
 
 
-def assert_bits(got, exp, what=""):
-    """torch.equal on the bit patterns; on a mismatch, say how many elements and how far."""
-    it = torch.int32 if got.dtype == torch.float32 else torch.int16
-    assert got.shape == exp.shape and got.dtype == exp.dtype
-    if torch.equal(got.contiguous().view(it), exp.contiguous().view(it)):
-        return
-    bad = got.contiguous().view(it) != exp.contiguous().view(it)
-    d = elt_ulps(got, exp, got.dtype)[bad]
-    raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements differ from RNE(true sum); "
-                         f"distance in representable values: min {int(d.min())}, max {int(d.max())}; "
-                         f"first at {[int(v) for v in bad.nonzero()[0]]}")
-
-
 @functools.lru_cache(maxsize=None)
-def operands(dtype, n, h, w, cin, k, s, in_extra=8, pool=False, seed=0, grid=None, cout=256):
+def operands(dtype, n, h, w, cin, k, s, in_extra=IN_LEAD, pool=False, seed=0, grid=None, cout=256):
     """Operands of one conv (shared by every tile / act / variant that runs it; never modified):
-    x_full [n][h][w][in_extra + cin] NHWC float64, wt [cout][cin][k][k], b [cout] and the exact
-    pre-activation z [n][cout][ho][wo]. pool: x_full is the (2h, 2w) map of the fused max-pool.
-    grid: (step_x, step_w, max|x|, max|w|) where a case needs another than pick_grid's."""
+    x_full [n][h][w][in_extra + cin + 8] NHWC float64 (the slice at channel in_extra, NaN around it),
+    wt [cout][cin][k][k], b [cout] and the exact pre-activation z [n][cout][ho][wo]. pool: x_full is the
+    (2h, 2w) map of the fused max-pool. grid: (step_x, step_w, max|x|, max|w|) where a case needs
+    another than pick_grid's. CPU only."""
     sx, sw, xm, wm = grid or (pick_grid(cin * k * k, dtype) + (X_MAX, W_MAX))
     assert cin * k * k * (xm / sx) * (wm / sw) < SPAN
     g = torch.Generator().manual_seed(1000 * seed + 17 * cin + k + s)
     up = 2 if pool else 1
-    o = types.SimpleNamespace(n=n, h=h, w=w, cin=cin, k=k, s=s, in_extra=in_extra, pool=pool, dtype=dtype)
-    o.x_full = dyadic((n, up * h, up * w, in_extra + cin), -xm, xm, sx, g)
+    o = types.SimpleNamespace(n=n, h=h, w=w, cin=cin, k=k, s=s, in_extra=in_extra, pool=pool, dtype=dtype,
+                              grid=(sx, sw, xm, wm))
+    xs = dyadic((n, up * h, up * w, in_extra + cin), -xm, xm, sx, g)[..., in_extra:]
+    o.x_full = nan_frame(xs, in_extra, IN_TAIL)
     o.wt = dyadic((cout, cin, k, k), -wm, wm, sw, g)
     o.b = dyadic((cout,), -B_MAX, B_MAX, B_STEP, g)
     tdt = TDT[dtype]
-    for t in (o.x_full, o.wt):  # the element type holds the operands exactly
+    for t in (xs, o.wt):  # the element type holds the operands exactly
         assert torch.equal(t.to(tdt).double(), t)
-    x = o.x_full[..., in_extra:].permute(0, 3, 1, 2)
+    x = xs.permute(0, 3, 1, 2)
     if pool:
         x = F.max_pool2d(x, 2, 2)  # exact
+    o.x = x
     o.z = F.conv2d(x, o.wt, o.b, s, k // 2)
     o.ho, o.wo = o.z.shape[2:]
     return o
@@ -128,34 +132,85 @@ def cpad_of(cout, dtype):
     return 32 if cout <= 32 else 64 if cout <= 64 else -(-cout // 128) * 128
 
 
-def launch(device, o, tile, cout, act=L.ACT_NONE, slope=0.0, out_extra=16, residual=None, layout=L.OUT_NHWC,
-           k_split=0, cpad=None):
-    """One conv through the C ABI on operands ``o`` (first ``cout`` channels); the raw output buffer."""
+def padding_rows(o, cout, cpad):
+    """Weight rows [cpad - cout][cin][k][k] and bias [cpad - cout] of the padding channels: the operands' own
+    channels cout .. cpad where ``operands`` drew that many, else fresh draws from the same grid."""
+    if o.wt.shape[0] >= cpad:
+        return o.wt[cout:cpad], o.b[cout:cpad]
+    sx, sw, xm, wm = o.grid
+    g = torch.Generator().manual_seed(77 + cout + 3 * cpad + o.cin)
+    return (dyadic((cpad - cout, o.cin, o.k, o.k), -wm, wm, sw, g), dyadic((cpad - cout,), -B_MAX, B_MAX, B_STEP, g))
+
+
+def packed(o, cout, cpad):
+    """wp [cpad][k][k][cin] in the element type and the fp32 bias [cpad], padding rows live."""
     tdt = TDT[o.dtype]
-    cpad = cpad or cpad_of(cout, o.dtype)
-    wp = torch.zeros(cpad, o.k, o.k, o.cin, dtype=tdt)
-    wp[:cout] = o.wt[:cout].permute(0, 2, 3, 1).to(tdt)
-    bp = torch.zeros(cpad)
-    bp[:cout] = o.b[:cout].float()
-    up = 2 if layout == L.OUT_NHWC_UP2 else 1
-    if layout == L.OUT_NCHW_F32:
-        y = torch.zeros(o.n, cout, o.ho, o.wo, dtype=torch.float32)
-    else:
-        y = torch.zeros(o.n, o.ho * up, o.wo * up, cout + out_extra, dtype=tdt)
+    wt, b = o.wt[:cout], o.b[:cout]
+    if cpad > cout:
+        wx, bx = padding_rows(o, cout, cpad)
+        assert bool(wx.flatten(1).any(1).all())  # no padding row is zero
+        wt, b = torch.cat([wt, wx]), torch.cat([b, bx])
+    wp = wt.permute(0, 2, 3, 1).contiguous().to(tdt)
+    assert torch.equal(wp.double(), wt.permute(0, 2, 3, 1))
+    return wp, b.float()
+
+
+def padding_stores(o, cout, cpad, act, slope, out_dt):
+    """What the padding channels cout .. cpad would store (element type ``out_dt``), from the reference."""
+    wx, bx = padding_rows(o, cout, cpad)
+    z = o.z[:, cout:cpad] if o.wt.shape[0] >= cpad else F.conv2d(o.x, wx, bx, o.s, o.k // 2)
+    return rne(apply_act(z, act, slope), out_dt)
+
+
+def check_live_padding(o, cout, cpad, act, slope, layout=L.OUT_NHWC):
+    """The live-padding condition of one cout < cout_pad case (CPU only): >= 90 % of what the padding
+    channels would store differs in its bits from the sentinel it would land on."""
+    f32 = layout == L.OUT_NCHW_F32
+    return live_padding_share(padding_stores(o, cout, cpad, act, slope, torch.float32 if f32 else TDT[o.dtype]),
+                              SENTINEL_F32 if f32 else SENTINEL)
+
+
+def conv_desc(o, tile, cout, act=L.ACT_NONE, slope=0.0, lead=OUT_LEAD, tail=OUT_TAIL, residual=False,
+              layout=L.OUT_NHWC, k_split=0, cpad=None):
+    """The ycx_conv2d descriptor of one case (no device)."""
     d = L.ConvDesc()
-    d.n, d.h, d.w, d.cin, d.in_c_off, d.in_c_stride = o.n, o.h, o.w, o.cin, o.in_extra, o.cin + o.in_extra
-    d.ho, d.wo, d.cout, d.cout_pad = o.ho, o.wo, cout, cpad
-    d.out_c_off, d.out_c_stride = (0, cout) if layout == L.OUT_NCHW_F32 else (out_extra, cout + out_extra)
+    d.n, d.h, d.w, d.cin, d.in_c_off, d.in_c_stride = o.n, o.h, o.w, o.cin, o.in_extra, o.x_full.shape[3]
+    d.ho, d.wo, d.cout, d.cout_pad = o.ho, o.wo, cout, cpad or cpad_of(cout, o.dtype)
+    d.out_c_off, d.out_c_stride = (1, cout + 2) if layout == L.OUT_NCHW_F32 else (lead, lead + cout + tail)
     d.kh = d.kw = o.k
     d.stride, d.pad, d.act, d.leaky_slope = o.s, 0 if o.pool else o.k // 2, act, slope
     d.dtype, d.out_layout, d.tile, d.k_split, d.in_pool = o.dtype, layout, tile, k_split, int(o.pool)
-    d.res_c_off, d.res_c_stride = 0, cout
-    xd, wd, bd, yd = o.x_full.to(tdt).to(device), wp.to(device), bp.to(device), y.to(device)
-    rd = residual.to(tdt).to(device) if residual is not None else None
+    if residual:
+        d.res_c_off, d.res_c_stride = IN_LEAD, IN_LEAD + cout + IN_TAIL
+    return d
+
+
+def input_guard(d, itemsize):
+    """Guard elements of the NHWC input of descriptor ``d`` (the (2h, 2w) map of a fused pool: pad 0)."""
+    return guard_elems(d.pad, d.w * (2 if d.in_pool else 1), d.in_c_stride, itemsize)
+
+
+def launch(device, o, tile, cout, act=L.ACT_NONE, slope=0.0, lead=OUT_LEAD, tail=OUT_TAIL, residual=None,
+           layout=L.OUT_NHWC, k_split=0, cpad=None):
+    """One conv through the C ABI on operands ``o`` (first ``cout`` channels); the raw output buffer.
+    residual: float64 [n][ho][wo][cout], passed as the slice at channel 8 of a NaN-framed, guarded buffer."""
+    tdt = TDT[o.dtype]
+    d = conv_desc(o, tile, cout, act, slope, lead, tail, residual is not None, layout, k_split, cpad)
+    wp, bp = packed(o, cout, d.cout_pad)
+    up = 2 if layout == L.OUT_NHWC_UP2 else 1
+    if layout == L.OUT_NCHW_F32:
+        y, sentinel = out_planes(o.n, cout, o.ho, o.wo), SENTINEL_F32
+    else:
+        y, sentinel = out_frame(o.n, o.ho * up, o.wo * up, cout, tdt, lead, tail), SENTINEL
+    xd = guarded(o.x_full.to(tdt), input_guard(d, tdt.itemsize), device)
+    wd, bd, yd = wp.to(device), bp.to(device), guarded_out(y, device)
+    rd = None
+    if residual is not None:
+        rd = guarded(nan_frame(residual).to(tdt), guard_elems(0, o.wo, d.res_c_stride, tdt.itemsize), device)
     st = L.stream_handle(device)
     if k_split > 1:
         nws = int(L.lib.ycx_conv_workspace_size(ctypes.byref(d)))
-        assert nws == k_split * o.n * o.ho * o.wo * cpad * 4
+        assert nws == k_split * o.n * o.ho * o.wo * d.cout_pad * 4
         ws = torch.full((nws // 4,), float('nan'), device=device)  # every partial must be overwritten
         L.check(L.lib.ycx_conv2d_ws(ctypes.byref(d), xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), yd.data_ptr(),
                                     L.ptr(rd), ws.data_ptr(), nws, st))
@@ -163,20 +218,18 @@ def launch(device, o, tile, cout, act=L.ACT_NONE, slope=0.0, out_extra=16, resid
         L.check(L.lib.ycx_conv2d(ctypes.byref(d), xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), yd.data_ptr(),
                                  L.ptr(rd), st))
     torch.cuda.synchronize()
-    return yd.cpu()
+    return fetch_out(yd, sentinel, what=f"tile {tile}")
 
 
-def expected(ref64, tdt, layout=L.OUT_NHWC, out_extra=16):
-    """The whole output buffer: RNE(ref) in the channel slice, zeros outside it."""
+def expected(ref64, tdt, layout=L.OUT_NHWC, lead=OUT_LEAD, tail=OUT_TAIL):
+    """The whole output buffer: RNE(ref) in the channel slice, the sentinel outside it."""
     if layout == L.OUT_NCHW_F32:
         check_inputs(ref64, torch.float32)
-        return ref64.float()
+        return expected_planes(ref64.float())
     r = ref64.permute(0, 2, 3, 1)
     if layout == L.OUT_NHWC_UP2:
         r = r.repeat_interleave(2, 1).repeat_interleave(2, 2)
-    exp = torch.zeros(*r.shape[:3], r.shape[3] + out_extra, dtype=tdt)
-    exp[..., out_extra:] = rne(r, tdt)
-    return exp
+    return expected_frame(rne(r, tdt), lead, tail)
 
 
 def run_acts(device, o, tile, cout, what, **kw):
@@ -186,7 +239,7 @@ def run_acts(device, o, tile, cout, what, **kw):
         ref = apply_act(o.z[:, :cout], act, slope)
         check_inputs(ref, tdt, what)
         got = launch(device, o, tile, cout, act, slope, **kw)
-        assert_bits(got, expected(ref, tdt, out_extra=kw.get('out_extra', 16)), f"{what} act {act} slope {slope}")
+        assert_bits(got, expected(ref, tdt), f"{what} act {act} slope {slope}")
 
 
 # tile -> (cout, cin) of the general cases (cout = the tile's channel width, cin its K step or twice it)
@@ -194,8 +247,10 @@ GENERAL = {1: (128, 64), 2: (64, 64), 3: (64, 64), 4: (128, 64), 5: (32, 32), 6:
            9: (128, 64), 10: (64, 64), 11: (256, 128), 12: (128, 64), 13: (64, 32), 14: (128, 32), 15: (64, 64),
            16: (128, 64), 17: (64, 32), 18: (64, 128), 24: (256, 64), 25: (256, 64), 26: (128, 64), 56: (64, 128)}
 KS = [(1, 1), (3, 1), (3, 2), (5, 1)]
+GENERAL_MAP = (2, 13, 11)
 
 
+@gpu
 @pytest.mark.parametrize('k,s', KS)
 @pytest.mark.parametrize('dtype', DT16)
 @pytest.mark.parametrize('tile', sorted(GENERAL))
@@ -203,15 +258,21 @@ def test_exact_general_tiles(device, tile, dtype, k, s):
     """Every general 16-bit tile (register-staged 1-7, LDS-DMA 9-18, 24-26, 56): ragged pixel tail,
     image borders, input and output channel slices."""
     cout, cin = GENERAL[tile]
-    o = operands(dtype, 2, 13, 11, cin, k, s)
+    o = operands(dtype, *GENERAL_MAP, cin, k, s)
     run_acts(device, o, tile, cout, f"tile {tile} dtype {dtype} k{k} s{s}")
 
 
+def f32_operands(k, s):
+    """Tile 8's operands: the bf16 cases' (cin 64), typed fp32."""
+    ob = operands(L.DT_BF16, *GENERAL_MAP, 64, k, s)
+    return types.SimpleNamespace(**{**vars(ob), 'dtype': L.DT_F32})
+
+
+@gpu
 @pytest.mark.parametrize('k,s', KS)
 def test_exact_f32_tile8(device, k, s):
     """Tile 8 (fp32 FMA chain) on the bf16 cases' operands: the fp32 output is the exact sum."""
-    ob = operands(L.DT_BF16, 2, 13, 11, 64, k, s)
-    o = types.SimpleNamespace(**{**vars(ob), 'dtype': L.DT_F32})
+    o = f32_operands(k, s)
     for act, slope in ACTS:
         ref = apply_act(o.z[:, :64], act, slope)
         got = launch(device, o, 8, 64, act, slope)
@@ -227,6 +288,7 @@ SPECIAL = [(19, 2, 16, 16, 64, 64, 3, 1), (19, 2, 32, 48, 64, 64, 3, 1), (20, 2,
            (22, 2, 96, 96, 64, 64, 1, 1)]
 
 
+@gpu
 @pytest.mark.parametrize('dtype', DT16)
 @pytest.mark.parametrize('tile,n,h,w,cin,cout,k,s', SPECIAL)
 def test_exact_special_kernels(device, tile, n, h, w, cin, cout, k, s, dtype):
@@ -238,63 +300,100 @@ def test_exact_special_kernels(device, tile, n, h, w, cin, cout, k, s, dtype):
 
 VARIANTS = [(t, v) for t in (3, 7, 16, 18, 56, 20, 48) for v in ('residual', 'up2', 'nchw_f32', 'cout_below_pad')
             if not (v == 'nchw_f32' and t in (20, 48))]  # the halo tiles store NHWC only
+VARIANT_WIDTH = {3: 64, 7: 128, 16: 128, 18: 64, 56: 64, 20: 128, 48: 64}
+VARIANT_ACT = (L.ACT_LEAKY, 0.125)
 
 
+def variant_case(tile, dtype, variant):
+    """(operands, cout, cout_pad or None, layout, lead, residual float64 NHWC or None, reference) of one case."""
+    h, w = (16, 16) if tile == 20 else (40, 40) if tile == 48 else (13, 11)
+    cin = 32 if tile == 7 else 64
+    width = VARIANT_WIDTH[tile]
+    o = operands(dtype, 2, h, w, cin, 3, 1)
+    act, slope = VARIANT_ACT
+    if variant == 'residual':
+        r = dyadic((2, o.ho, o.wo, width), -4, 4, 1 / 16, torch.Generator().manual_seed(tile))
+        return o, width, None, L.OUT_NHWC, OUT_LEAD, r, apply_act(o.z[:, :width], act, slope) + r.permute(0, 3, 1, 2)
+    if variant == 'up2':
+        return o, width, None, L.OUT_NHWC_UP2, UP2_LEAD, None, apply_act(o.z[:, :width], act, slope)
+    if variant == 'nchw_f32':  # 127 / 255 channels, padded to the next tile width, at plane offset 1
+        cout = 2 * width - 1
+        return o, cout, 2 * width, L.OUT_NCHW_F32, OUT_LEAD, None, apply_act(o.z[:, :cout], act, slope)
+    cout = width - 8
+    return o, cout, width, L.OUT_NHWC, OUT_LEAD, None, apply_act(o.z[:, :cout], act, slope)
+
+
+@gpu
 @pytest.mark.parametrize('dtype', DT16)
 @pytest.mark.parametrize('tile,variant', VARIANTS)
 def test_exact_epilogue_variants(device, tile, dtype, variant):
-    """The epilogue's other stores: a residual on the 1/16 grid (the fp32 add is exact, one rounding),
-    the x2 upsample store, the fp32 NCHW store (the exact sum, no rounding at all) and cout < cout_pad."""
-    h, w = (16, 16) if tile == 20 else (40, 40) if tile == 48 else (13, 11)
-    cin = 32 if tile == 7 else 64
-    width = {3: 64, 7: 128, 16: 128, 18: 64, 56: 64, 20: 128, 48: 64}[tile]
-    o = operands(dtype, 2, h, w, cin, 3, 1)
-    tdt, act, slope = TDT[dtype], L.ACT_LEAKY, 0.125
+    """The epilogue's other stores: a residual on the 1/16 grid (the fp32 add is exact, one rounding; the
+    residual a NaN-framed slice), the x2 upsample store, the fp32 NCHW store (the exact sum, no rounding at
+    all; 127 / 255 of 128 / 256 channels at plane offset 1) and cout < cout_pad, padding rows live."""
+    o, cout, cpad, layout, lead, r, ref = variant_case(tile, dtype, variant)
+    tdt, (act, slope) = TDT[dtype], VARIANT_ACT
     what = f"tile {tile} dtype {dtype} {variant}"
-    if variant == 'residual':
-        r = dyadic((2, o.ho, o.wo, width), -4, 4, 1 / 16, torch.Generator().manual_seed(tile))
-        ref = apply_act(o.z[:, :width], act, slope) + r.permute(0, 3, 1, 2)
+    if layout != L.OUT_NCHW_F32:
         check_inputs(ref, tdt, what)
-        got = launch(device, o, tile, width, act, slope, residual=r)
-        assert_bits(got, expected(ref, tdt), what)
-    elif variant == 'up2':
-        ref = apply_act(o.z[:, :width], act, slope)
-        check_inputs(ref, tdt, what)
-        got = launch(device, o, tile, width, act, slope, layout=L.OUT_NHWC_UP2, out_extra=8)
-        assert_bits(got, expected(ref, tdt, L.OUT_NHWC_UP2, 8), what)
-    elif variant == 'nchw_f32':
-        cout = 2 * width - 1  # 127 / 255 channels, padded to the next tile width
-        ref = apply_act(o.z[:, :cout], act, slope)
-        got = launch(device, o, tile, cout, act, slope, layout=L.OUT_NCHW_F32, cpad=2 * width)
-        assert_bits(got, expected(ref, tdt, L.OUT_NCHW_F32), what)
-    else:
-        cout = width - 8
-        ref = apply_act(o.z[:, :cout], act, slope)
-        check_inputs(ref, tdt, what)
-        got = launch(device, o, tile, cout, act, slope, cpad=width)
-        assert_bits(got, expected(ref, tdt), what)
+    got = launch(device, o, tile, cout, act, slope, lead=lead, residual=r, layout=layout, cpad=cpad)
+    assert_bits(got, expected(ref, tdt, layout, lead), what)
 
 
+UP2_BELOW_PAD = (16, 120, 128)  # tile, cout, cout_pad
+
+
+@gpu
 @pytest.mark.parametrize('dtype', DT16)
-@pytest.mark.parametrize('tile,h,w,cin,cout,cpad,k,s', [(22, 13, 11, 128, 248, 256, 1, 1), (23, 16, 32, 64, 48, 64, 3, 1),
-                                                        (49, 40, 40, 64, 120, 128, 3, 1), (50, 31, 63, 64, 96, 128, 3, 2)])
-def test_exact_cout_below_pad(device, tile, h, w, cin, cout, cpad, k, s, dtype):
-    """cout < cout_pad on the kernels with their own epilogues (padding channels are not stored)."""
-    o = operands(dtype, 2, h, w, cin, k, s)
-    ref = apply_act(o.z[:, :cout], L.ACT_LEAKY, 0.25)
+def test_exact_up2_cout_below_pad(device, dtype):
+    """The x2 store with cout < cout_pad (tile 16, 120 of 128): it writes four pixels per result, so a
+    spilled padding channel would land four times."""
+    tile, cout, cpad = UP2_BELOW_PAD
+    o = operands(dtype, *GENERAL_MAP, 64, 3, 1)
+    act, slope = VARIANT_ACT
+    ref = apply_act(o.z[:, :cout], act, slope)
     check_inputs(ref, TDT[dtype])
-    got = launch(device, o, tile, cout, L.ACT_LEAKY, 0.25, cpad=cpad)
+    got = launch(device, o, tile, cout, act, slope, lead=UP2_LEAD, layout=L.OUT_NHWC_UP2, cpad=cpad)
+    assert_bits(got, expected(ref, TDT[dtype], L.OUT_NHWC_UP2, UP2_LEAD), f"tile {tile} up2 cout {cout} < {cpad}")
+
+
+BELOW_PAD = [(22, 13, 11, 128, 248, 256, 1, 1), (23, 16, 32, 64, 48, 64, 3, 1), (49, 40, 40, 64, 120, 128, 3, 1),
+             (50, 31, 63, 64, 96, 128, 3, 2)]
+BELOW_PAD_ACT = (L.ACT_LEAKY, 0.25)
+
+
+@gpu
+@pytest.mark.parametrize('dtype', DT16)
+@pytest.mark.parametrize('tile,h,w,cin,cout,cpad,k,s', BELOW_PAD)
+def test_exact_cout_below_pad(device, tile, h, w, cin, cout, cpad, k, s, dtype):
+    """cout < cout_pad on the kernels with their own epilogues (padding channels are computed on live
+    rows and not stored)."""
+    o = operands(dtype, 2, h, w, cin, k, s)
+    act, slope = BELOW_PAD_ACT
+    ref = apply_act(o.z[:, :cout], act, slope)
+    check_inputs(ref, TDT[dtype])
+    got = launch(device, o, tile, cout, act, slope, cpad=cpad)
     assert_bits(got, expected(ref, TDT[dtype]), f"tile {tile} cout {cout} < {cpad}")
 
 
+SPLITK_SHAPES = [(256, 3, 1), (512, 1, 1), (128, 3, 2), (256, 3, 2)]  # cin, k, s
+SPLITK_TILES = [(16, 128), (18, 64), (56, 64)]
+SPLITK_ACT = (L.ACT_LEAKY, 0.125)
+
+
+def splitk_residual(o, cout):
+    return dyadic((2, o.ho, o.wo, cout), -4, 4, 1 / 16, torch.Generator().manual_seed(5))
+
+
+@gpu
 @pytest.mark.parametrize('dtype', DT16)
-@pytest.mark.parametrize('cin,k,s', [(256, 3, 1), (512, 1, 1), (128, 3, 2), (256, 3, 2)])
-@pytest.mark.parametrize('tile,cout', [(16, 128), (18, 64), (56, 64)])
+@pytest.mark.parametrize('cin,k,s', SPLITK_SHAPES)
+@pytest.mark.parametrize('tile,cout', SPLITK_TILES)
 def test_exact_splitk(device, tile, cout, cin, k, s, dtype):
     """k_split 2, 3, 4: the reduce's store is RNE(true sum) and equals the unsplit launch bit for bit
-    (cin 128 / stride 2 on tile 16: the chunk-major K order); then a residual through the reduce."""
-    o = operands(dtype, 2, 13, 11, cin, k, s)
-    tdt, act, slope = TDT[dtype], L.ACT_LEAKY, 0.125
+    (cin 128 / stride 2 on tile 16: the chunk-major K order); then a residual through the reduce, read
+    from a NaN-framed slice."""
+    o = operands(dtype, *GENERAL_MAP, cin, k, s)
+    tdt, (act, slope) = TDT[dtype], SPLITK_ACT
     ref = apply_act(o.z[:, :cout], act, slope)
     check_inputs(ref, tdt)
     exp = expected(ref, tdt)
@@ -304,15 +403,19 @@ def test_exact_splitk(device, tile, cout, cin, k, s, dtype):
         got = launch(device, o, tile, cout, act, slope, k_split=ks)
         assert_bits(got, exp, f"tile {tile} k_split {ks}")
         assert torch.equal(got.view(torch.int16), unsplit.view(torch.int16))
-    r = dyadic((2, o.ho, o.wo, cout), -4, 4, 1 / 16, torch.Generator().manual_seed(5))
+    r = splitk_residual(o, cout)
     ref = ref + r.permute(0, 3, 1, 2)
     check_inputs(ref, tdt)
     assert_bits(launch(device, o, tile, cout, act, slope, k_split=3, residual=r), expected(ref, tdt),
                 f"tile {tile} k_split 3 + residual")
 
 
+KCM = [(2, 40, 40, 128), (1, 33, 47, 120)]  # n, h, w, cout
+
+
+@gpu
 @pytest.mark.parametrize('dtype', DT16)
-@pytest.mark.parametrize('n,h,w,cout', [(2, 40, 40, 128), (1, 33, 47, 120)])
+@pytest.mark.parametrize('n,h,w,cout', KCM)
 def test_exact_tile16_s2_cin128_chunk_major(device, n, h, w, cout, dtype):
     """Tile 16's chunk-major paired-tap K order (3x3 / s2 at cin 128), unsplit: odd map sizes put taps
     outside the image; several pixel tiles; cout < cout_pad."""
@@ -320,13 +423,16 @@ def test_exact_tile16_s2_cin128_chunk_major(device, n, h, w, cout, dtype):
     run_acts(device, o, 16, cout, f"tile 16 KCM {h}x{w}")
 
 
+POOL = [(16, 128, 64), (16, 128, 256), (18, 64, 64), (18, 64, 256), (25, 256, 64), (25, 256, 256)]  # tile, cout, cin
+
+
+@gpu
 @pytest.mark.parametrize('dtype', DT16)
-@pytest.mark.parametrize('tile,cout,cin', [(16, 128, 64), (16, 128, 256), (18, 64, 64), (18, 64, 256), (25, 256, 64),
-                                           (25, 256, 256)])
+@pytest.mark.parametrize('tile,cout,cin', POOL)
 def test_exact_fused_pool(device, tile, cout, cin, dtype):
     """in_pool: the k2 s2 max-pool formed in the operand staging is exact on the grid, so the
-    pooled 1x1 conv is RNE(true sum) like any other."""
-    o = operands(dtype, 2, 13, 11, cin, 1, 1, pool=True)
+    pooled 1x1 conv is RNE(true sum) like any other; the (2h, 2w) map is framed like any input."""
+    o = operands(dtype, *GENERAL_MAP, cin, 1, 1, pool=True)
     run_acts(device, o, tile, cout, f"tile {tile} in_pool cin {cin}")
 
 
@@ -339,93 +445,137 @@ def _desc_1x1(n, h, w, cin, cout, cpad, in_off, in_stride, out_off, out_stride, 
     return d
 
 
-@pytest.mark.parametrize('dtype', DT16)
-@pytest.mark.parametrize('cin,cout2,store1', [(64, 128, True), (128, 120, False), (256, 256, True)])
-def test_exact_conv2d_pair(device, cin, cout2, store1, dtype):
-    """ycx_conv2d_pair: y1 = RNE(sum1) (act none), then the second conv on those elements with
-    w2 in {-1, 0, 1} and bias on the 1/16 grid: y1 (when stored) and y2 bit-exact to the reference
-    chain. y1's elements are multiples of u1 = step_x * step_w, so the second conv's span is
-    256 * max|y1|/u1 * 1 < 2^20, asserted from the reference. That bound caps y1 at 2^12 u1: an
-    eleven-bit fp16 element then needs rounding only in the top of its range, so the >= 10 % rounded
-    condition is asserted on y2 in both types and on y1 in bf16; fp16 y1 rounding is covered by every
-    single-conv case."""
-    n, h, w = 2, 13, 11
+PAIR = [(64, 128, True), (128, 120, False), (256, 256, True)]  # cin, cout2, y1 stored
+PAIR_MAP = (2, 13, 11)
+PAIR_ACT2 = (L.ACT_LEAKY, 0.25)
+
+
+@functools.lru_cache(maxsize=None)
+def pair_case(dtype, cin, cout2):
+    """Operands, references and descriptors of one ycx_conv2d_pair case (CPU only; docstring of the test)."""
+    n, h, w = PAIR_MAP
     tdt = TDT[dtype]
     xm = 2.0 if cin == 256 else 4.0
-    o = operands(dtype, n, h, w, cin, 1, 1, grid=(1 / 4, 1 / 4, xm, 2.0))
-    u1 = 1 / 16
-    z1 = o.z  # 256 channels
-    if dtype == L.DT_BF16:
-        check_inputs(z1, tdt, "pair y1")
-    y1 = rne(z1, tdt).double()
-    assert 256 * float(y1.abs().max()) / u1 * 1 < SPAN
+    c = types.SimpleNamespace(o=operands(dtype, n, h, w, cin, 1, 1, grid=(1 / 4, 1 / 4, xm, 2.0)), u1=1 / 16)
+    c.z1 = c.o.z  # 256 channels
+    y1 = rne(c.z1, tdt).double()
+    assert 256 * float(y1.abs().max()) / c.u1 * 1 < SPAN
     g = torch.Generator().manual_seed(cin)
     w2 = dyadic((cout2, 256), -1, 1, 1.0, g)
     b2 = dyadic((cout2,), -B_MAX, B_MAX, B_STEP, g)
-    z2 = apply_act(torch.einsum('nchw,oc->nohw', y1, w2) + b2[None, :, None, None], L.ACT_LEAKY, 0.25)
-    check_inputs(z2, tdt, "pair y2")
-    cpad2 = 128 if cout2 <= 128 else 256
+    c.cpad2 = 128 if cout2 <= 128 else 256
+    if c.cpad2 > cout2:  # live padding rows, drawn after (and apart from) the case's own operands
+        gp = torch.Generator().manual_seed(1000 + cin)
+        w2 = torch.cat([w2, dyadic((c.cpad2 - cout2, 256), -1, 1, 1.0, gp)])
+        b2 = torch.cat([b2, dyadic((c.cpad2 - cout2,), -B_MAX, B_MAX, B_STEP, gp)])
+        assert bool(w2[cout2:].any(1).all())
+    z2 = apply_act(torch.einsum('nchw,oc->nohw', y1, w2) + b2[None, :, None, None], *PAIR_ACT2)
+    c.z2, c.z2_pad, c.w2, c.b2 = z2[:, :cout2], z2[:, cout2:], w2, b2
+    ya_stride = OUT_LEAD + 256 + OUT_TAIL
+    c.da = _desc_1x1(n, h, w, cin, 256, 256, c.o.in_extra, c.o.x_full.shape[3], OUT_LEAD, ya_stride, L.ACT_NONE, 0.0,
+                     dtype)
+    c.db = _desc_1x1(n, h, w, 256, cout2, c.cpad2, OUT_LEAD, ya_stride, OUT_LEAD, OUT_LEAD + cout2 + OUT_TAIL,
+                     *PAIR_ACT2, dtype)
+    return c
+
+
+@gpu
+@pytest.mark.parametrize('dtype', DT16)
+@pytest.mark.parametrize('cin,cout2,store1', PAIR)
+def test_exact_conv2d_pair(device, cin, cout2, store1, dtype):
+    """ycx_conv2d_pair: y1 = RNE(sum1) (act none), then the second conv on those elements with
+    w2 in {-1, 0, 1} and bias on the 1/16 grid: y1 (when stored) and y2 bit-exact to the reference
+    chain, both in framed buffers; y1's buffer untouched when it is not stored. y1's elements are
+    multiples of u1 = step_x * step_w, so the second conv's span is 256 * max|y1|/u1 * 1 < 2^20, asserted
+    from the reference. That bound caps y1 at 2^12 u1: an eleven-bit fp16 element then needs rounding only
+    in the top of its range, so the >= 10 % rounded condition is asserted on y2 in both types and on y1 in
+    bf16; fp16 y1 rounding is covered by every single-conv case."""
+    n, h, w = PAIR_MAP
+    tdt = TDT[dtype]
+    c = pair_case(dtype, cin, cout2)
+    o = c.o
+    if dtype == L.DT_BF16:
+        check_inputs(c.z1, tdt, "pair y1")
+    check_inputs(c.z2, tdt, "pair y2")
     w1p = o.wt[:, :, 0, 0].to(tdt)
-    w2p = torch.zeros(cpad2, 256, dtype=tdt)
-    w2p[:cout2] = w2.to(tdt)
-    b2p = torch.zeros(cpad2)
-    b2p[:cout2] = b2.float()
-    xd, w1d, b1d, w2d, b2d = [t.to(device) for t in (o.x_full.to(tdt), w1p, o.b.float(), w2p, b2p)]
-    ya = torch.zeros(n, h, w, 256 + 16, dtype=tdt, device=device)
-    yb = torch.zeros(n, h, w, cout2 + 8, dtype=tdt, device=device)
-    da = _desc_1x1(n, h, w, cin, 256, 256, 8, cin + 8, 16, 272, L.ACT_NONE, 0.0, dtype)
-    db = _desc_1x1(n, h, w, 256, cout2, cpad2, 16, 272, 8, cout2 + 8, L.ACT_LEAKY, 0.25, dtype)
-    L.check(L.lib.ycx_conv2d_pair(ctypes.byref(da), ctypes.byref(db), xd.data_ptr(), w1d.data_ptr(), b1d.data_ptr(),
+    xd = guarded(o.x_full.to(tdt), input_guard(c.da, tdt.itemsize), device)
+    w1d, b1d, w2d, b2d = [t.to(device) for t in (w1p, o.b.float(), c.w2.to(tdt), c.b2.float())]
+    ya = guarded_out(out_frame(n, h, w, 256, tdt), device)
+    yb = guarded_out(out_frame(n, h, w, cout2, tdt), device)
+    L.check(L.lib.ycx_conv2d_pair(ctypes.byref(c.da), ctypes.byref(c.db), xd.data_ptr(), w1d.data_ptr(), b1d.data_ptr(),
                                   ya.data_ptr() if store1 else None, w2d.data_ptr(), b2d.data_ptr(), yb.data_ptr(),
                                   L.stream_handle(device)))
     torch.cuda.synchronize()
-    assert_bits(yb.cpu(), expected(z2, tdt, out_extra=8), "pair y2")
+    assert_bits(fetch_out(yb, SENTINEL, what="pair y2"), expected(c.z2, tdt), "pair y2")
+    got_a = fetch_out(ya, SENTINEL, what="pair y1")
     if store1:
-        assert_bits(ya.cpu(), expected(z1, tdt, out_extra=16), "pair y1")
+        assert_bits(got_a, expected(c.z1, tdt), "pair y1")
     else:
-        assert not ya.any()
+        assert_bits(got_a, out_frame(n, h, w, 256, tdt), "pair y1 (not stored)")
 
 
 STEM_GRID = dict(sx=1 / 64, sw=1 / 32)  # 27 * 256 * 64 < 2^20; eight significand bits hold both exactly
+STEM_SHAPES = [(17, 19, 32), (18, 32, 32), (9, 64, 64)]  # wo % 16 == 0: the MFMA stem
+STEM_DTYPES = [L.DT_BF16, L.DT_F16, L.DT_F32]
 
 
-@pytest.mark.parametrize('dtype', [L.DT_BF16, L.DT_F16, L.DT_F32])
-@pytest.mark.parametrize('s', [1, 2])
-@pytest.mark.parametrize('h,w,cout', [(17, 19, 32), (18, 32, 32), (9, 64, 64)])  # wo % 16 == 0: the MFMA stem
-def test_exact_stem(device, h, w, cout, s, dtype):
-    """ycx_stem_conv, scalar and MFMA: the fp32 image and weights sit on a grid that the in-kernel
-    conversion to the element type keeps unchanged; the output is RNE(true sum)."""
+def image_guard(pad, w):
+    """Guard floats of an fp32 NCHW image (16-byte aligned behind it; the stems ask for 8)."""
+    return guard_elems(pad, w, 1, 4)
+
+
+@functools.lru_cache(maxsize=None)
+def stem_case(h, w, cout, s):
+    """Image, weights, bias (float64) and the exact pre-activation of one ycx_stem_conv case (CPU only)."""
     n, cin, k = 2, 3, 3
     assert 27 * (X_MAX / STEM_GRID['sx']) * (W_MAX / STEM_GRID['sw']) < SPAN
     g = torch.Generator().manual_seed(h * w + s)
-    x = dyadic((n, cin, h, w), -X_MAX, X_MAX, STEM_GRID['sx'], g)
-    wt = dyadic((cout, cin, k, k), -W_MAX, W_MAX, STEM_GRID['sw'], g)
-    b = dyadic((cout,), -B_MAX, B_MAX, B_STEP, g)
-    tdt = TDT[dtype]
-    for t in (x, wt):
+    c = types.SimpleNamespace(n=n, h=h, w=w, s=s, cout=cout)
+    c.x = dyadic((n, cin, h, w), -X_MAX, X_MAX, STEM_GRID['sx'], g)
+    c.wt = dyadic((cout, cin, k, k), -W_MAX, W_MAX, STEM_GRID['sw'], g)
+    c.b = dyadic((cout,), -B_MAX, B_MAX, B_STEP, g)
+    for t in (c.x, c.wt):
         assert torch.equal(t.to(torch.bfloat16).double(), t) and torch.equal(t.to(torch.float16).double(), t)
-    z = F.conv2d(x, wt, b, s, 1)
-    ho, wo = z.shape[2:]
-    xd, wd, bd = x.float().to(device), wt.permute(2, 3, 1, 0).contiguous().float().to(device), b.float().to(device)
+    c.z = F.conv2d(c.x, c.wt, c.b, s, 1)
+    c.ho, c.wo = c.z.shape[2:]
+    return c
+
+
+def stem_desc(c, dtype, act, slope):
+    d = L.ConvDesc()
+    d.n, d.h, d.w, d.cin, d.in_c_off, d.in_c_stride = c.n, c.h, c.w, 3, 0, 3
+    d.ho, d.wo, d.cout, d.cout_pad = c.ho, c.wo, c.cout, c.cout
+    d.out_c_off, d.out_c_stride = STEM_LEAD, STEM_LEAD + c.cout + OUT_TAIL
+    d.kh = d.kw = 3
+    d.stride, d.pad, d.act, d.leaky_slope, d.dtype, d.out_layout = c.s, 1, act, slope, dtype, L.OUT_NHWC
+    return d
+
+
+@gpu
+@pytest.mark.parametrize('dtype', STEM_DTYPES)
+@pytest.mark.parametrize('s', [1, 2])
+@pytest.mark.parametrize('h,w,cout', STEM_SHAPES)
+def test_exact_stem(device, h, w, cout, s, dtype):
+    """ycx_stem_conv, scalar and MFMA: the fp32 image (between NaN guards) and weights sit on a grid that
+    the in-kernel conversion to the element type keeps unchanged; the output is RNE(true sum)."""
+    c = stem_case(h, w, cout, s)
+    tdt = TDT[dtype]
+    xd = guarded(c.x.float(), image_guard(1, w), device)
+    wd, bd = c.wt.permute(2, 3, 1, 0).contiguous().float().to(device), c.b.float().to(device)
     for act, slope in ACTS:
-        ref = apply_act(z, act, slope)
+        ref = apply_act(c.z, act, slope)
         check_inputs(ref, tdt, "stem")
-        d = L.ConvDesc()
-        d.n, d.h, d.w, d.cin, d.in_c_off, d.in_c_stride = n, h, w, cin, 0, cin
-        d.ho, d.wo, d.cout, d.cout_pad, d.out_c_off, d.out_c_stride = ho, wo, cout, cout, 8, cout + 8
-        d.kh = d.kw = k
-        d.stride, d.pad, d.act, d.leaky_slope, d.dtype, d.out_layout = s, 1, act, slope, dtype, L.OUT_NHWC
-        yd = torch.zeros(n, ho, wo, cout + 8, dtype=tdt, device=device)
+        d = stem_desc(c, dtype, act, slope)
+        yd = guarded_out(out_frame(c.n, c.ho, c.wo, cout, tdt, STEM_LEAD), device)
         L.check(L.lib.ycx_stem_conv(ctypes.byref(d), xd.data_ptr(), wd.data_ptr(), bd.data_ptr(), yd.data_ptr(),
                                     L.stream_handle(device)))
         torch.cuda.synchronize()
-        assert_bits(yd.cpu(), expected(ref, tdt, out_extra=8), f"stem {h}x{w} s{s} dtype {dtype} act {act} {slope}")
+        what = f"stem {h}x{w} s{s} dtype {dtype} act {act} {slope}"
+        assert_bits(fetch_out(yd, SENTINEL, what=what), expected(ref, tdt, lead=STEM_LEAD), what)
 
 
-def run_stem2(device, dtype, stem_s, act, slope, x, ws, bs, wc, bc, cout):
-    """ycx_stem_conv2 on float64 operands (ws [32][3][3][3], wc [cout][32][3][3]); the raw output."""
-    n, _, h, w = x.shape
-    tdt = TDT[dtype]
+def stem2_descs(n, h, w, dtype, stem_s, act, slope, cout):
+    """ycx_stem_conv2's two descriptors (no device)."""
     sh, sw = (h - 1) // stem_s + 1, (w - 1) // stem_s + 1
     ho, wo = (sh - 1) // 2 + 1, (sw - 1) // 2 + 1
     ds, dc = L.ConvDesc(), L.ConvDesc()
@@ -434,25 +584,68 @@ def run_stem2(device, dtype, stem_s, act, slope, x, ws, bs, wc, bc, cout):
     ds.kh = ds.kw = 3
     ds.stride, ds.pad, ds.act, ds.leaky_slope, ds.dtype, ds.out_layout = stem_s, 1, act, slope, dtype, L.OUT_NHWC
     dc.n, dc.h, dc.w, dc.cin, dc.in_c_off, dc.in_c_stride = n, sh, sw, 32, 0, 32
-    dc.ho, dc.wo, dc.cout, dc.cout_pad, dc.out_c_off, dc.out_c_stride = ho, wo, cout, 64, 8, cout + 8
+    dc.ho, dc.wo, dc.cout, dc.cout_pad = ho, wo, cout, 64
+    dc.out_c_off, dc.out_c_stride = STEM_LEAD, STEM_LEAD + cout + OUT_TAIL
     dc.kh = dc.kw = 3
     dc.stride, dc.pad, dc.act, dc.leaky_slope, dc.dtype, dc.out_layout = 2, 1, act, slope, dtype, L.OUT_NHWC
-    wcp = torch.zeros(64, 3, 3, 32, dtype=tdt)
-    wcp[:cout] = wc.permute(0, 2, 3, 1).to(tdt)
-    assert torch.equal(wcp[:cout].double(), wc.permute(0, 2, 3, 1))
-    bcp = torch.zeros(64)
-    bcp[:cout] = bc.float()
-    y = torch.zeros(n, ho, wo, cout + 8, dtype=tdt)
-    t = [v.to(device) for v in (x.float(), ws.permute(2, 3, 1, 0).contiguous().float(), bs.float(), wcp, bcp, y)]
-    L.check(L.lib.ycx_stem_conv2(ctypes.byref(ds), ctypes.byref(dc), *[v.data_ptr() for v in t],
-                                 L.stream_handle(device)))
+    return ds, dc
+
+
+def run_stem2(device, dtype, stem_s, act, slope, x, ws, bs, wc, bc, cout):
+    """ycx_stem_conv2 on float64 operands (ws [32][3][3][3], wc [64][32][3][3]: rows cout .. 64 are the
+    live padding rows; bc [64]); the raw output buffer."""
+    n, _, h, w = x.shape
+    tdt = TDT[dtype]
+    ds, dc = stem2_descs(n, h, w, dtype, stem_s, act, slope, cout)
+    assert wc.shape[0] == 64 and bc.shape[0] == 64 and bool(wc.flatten(1).any(1).all())
+    wcp = wc.permute(0, 2, 3, 1).contiguous().to(tdt)
+    assert torch.equal(wcp.double(), wc.permute(0, 2, 3, 1))
+    xd = guarded(x.float(), image_guard(1, w), device)
+    yd = guarded_out(out_frame(n, dc.ho, dc.wo, cout, tdt, STEM_LEAD), device)
+    t = [v.to(device) for v in (ws.permute(2, 3, 1, 0).contiguous().float(), bs.float(), wcp, bc.float())]
+    L.check(L.lib.ycx_stem_conv2(ctypes.byref(ds), ctypes.byref(dc), xd.data_ptr(), *[v.data_ptr() for v in t],
+                                 yd.data_ptr(), L.stream_handle(device)))
     torch.cuda.synchronize()
-    return t[5].cpu()
+    return fetch_out(yd, SENTINEL, what="stem2")
 
 
+STEM2_ACTS = [(L.ACT_NONE, 0.0), (L.ACT_LEAKY, 0.125)]
+STEM2 = [(1, 64, (2, 32, 64)), (2, 48, (2, 64, 128))]  # stem stride, cout, (n, h, w)
+
+
+@functools.lru_cache(maxsize=None)
+def stem2_case(dtype, stem_s, cout, nhw, act, slope):
+    """Operands and references of one ycx_stem_conv2 case (CPU only; docstring of test_exact_stem2). wc and
+    bc hold all 64 padded channels: rows cout .. 64 are drawn apart, on the same grid."""
+    n, h, w = nhw
+    tdt = TDT[dtype]
+    g = torch.Generator().manual_seed(7 + stem_s)
+    c = types.SimpleNamespace(cout=cout)
+    if act == L.ACT_NONE:  # stem sums in units of 1/16
+        c.x, c.ws, u = dyadic((n, 3, h, w), -4, 4, 1 / 4, g), dyadic((32, 3, 3, 3), -2, 2, 1 / 4, g), 1 / 16
+        c.bs = dyadic((32,), -B_MAX, B_MAX, 1 / 16, g)
+    else:                  # stem sums in units of 1/4, the stem map in units of slope / 4
+        c.x, c.ws, u = dyadic((n, 3, h, w), -2, 2, 1 / 2, g), dyadic((32, 3, 3, 3), -1, 1, 1 / 2, g), slope / 4
+        c.bs = dyadic((32,), -B_MAX, B_MAX, 1 / 4, g)
+    wc = dyadic((cout, 32, 3, 3), -1, 1, 1 / 2, g)
+    bc = dyadic((cout,), -B_MAX, B_MAX, B_STEP, g)
+    if cout < 64:
+        gp = torch.Generator().manual_seed(1007 + stem_s)
+        wc = torch.cat([wc, dyadic((64 - cout, 32, 3, 3), -1, 1, 1 / 2, gp)])
+        bc = torch.cat([bc, dyadic((64 - cout,), -B_MAX, B_MAX, B_STEP, gp)])
+    c.wc, c.bc = wc, bc
+    c.z1 = apply_act(F.conv2d(c.x, c.ws, c.bs, stem_s, 1), act, slope)
+    mid = rne(c.z1, tdt).double()
+    assert torch.equal(mid / u, (mid / u).round()) and 288 * float(mid.abs().max()) / u * 2 < SPAN
+    z2 = apply_act(F.conv2d(mid, wc, bc, 2, 1), act, slope)
+    c.ref, c.ref_pad = z2[:, :cout], z2[:, cout:]
+    return c
+
+
+@gpu
 @pytest.mark.parametrize('dtype', DT16)
-@pytest.mark.parametrize('act,slope', [(L.ACT_NONE, 0.0), (L.ACT_LEAKY, 0.125)])
-@pytest.mark.parametrize('stem_s,cout,nhw', [(1, 64, (2, 32, 64)), (2, 48, (2, 64, 128))])
+@pytest.mark.parametrize('act,slope', STEM2_ACTS)
+@pytest.mark.parametrize('stem_s,cout,nhw', STEM2)
 def test_exact_stem2(device, stem_s, cout, nhw, act, slope, dtype):
     """ycx_stem_conv2: the stem map is rounded to the element type as the kernel keeps it in LDS, the
     second conv (w2 in 1/2 steps within +-1) runs on those elements; output bit-exact. The second
@@ -460,62 +653,66 @@ def test_exact_stem2(device, stem_s, cout, nhw, act, slope, dtype):
     asserted from the reference. Act none: image and stem weights on the base grid, the bf16 stem map
     needs rounding (|mid| up to ~75 in units of 1/16). Leaky: the slope makes the unit 8 times finer,
     so image and stem weights move to 1/2 steps within +-2 / +-1 (no stem-map rounding there, nor in
-    fp16, whose eleven bits hold every stem sum the span bound allows)."""
-    n, h, w = nhw
+    fp16, whose eleven bits hold every stem sum the span bound allows). cout 48: channels 48 .. 63 run on
+    live rows."""
     tdt = TDT[dtype]
-    g = torch.Generator().manual_seed(7 + stem_s)
-    if act == L.ACT_NONE:  # stem sums in units of 1/16
-        x, ws, u = dyadic((n, 3, h, w), -4, 4, 1 / 4, g), dyadic((32, 3, 3, 3), -2, 2, 1 / 4, g), 1 / 16
-        bs = dyadic((32,), -B_MAX, B_MAX, 1 / 16, g)
-    else:                  # stem sums in units of 1/4, the stem map in units of slope / 4
-        x, ws, u = dyadic((n, 3, h, w), -2, 2, 1 / 2, g), dyadic((32, 3, 3, 3), -1, 1, 1 / 2, g), slope / 4
-        bs = dyadic((32,), -B_MAX, B_MAX, 1 / 4, g)
-    wc = dyadic((cout, 32, 3, 3), -1, 1, 1 / 2, g)
-    bc = dyadic((cout,), -B_MAX, B_MAX, B_STEP, g)
-    z1 = apply_act(F.conv2d(x, ws, bs, stem_s, 1), act, slope)
-    mid = rne(z1, tdt).double()
-    assert torch.equal(mid / u, (mid / u).round()) and 288 * float(mid.abs().max()) / u * 2 < SPAN
+    c = stem2_case(dtype, stem_s, cout, nhw, act, slope)
     if act == L.ACT_NONE and dtype == L.DT_BF16:
-        assert rounding_stats(z1, tdt)[0] >= MIN_ROUNDED  # the stem map's rounding is part of the case
-    ref = apply_act(F.conv2d(mid, wc, bc, 2, 1), act, slope)
-    check_inputs(ref, tdt, "stem2")
-    got = run_stem2(device, dtype, stem_s, act, slope, x, ws, bs, wc, bc, cout)
-    assert_bits(got, expected(ref, tdt, out_extra=8), f"stem2 s{stem_s} cout {cout} act {act} dtype {dtype}")
+        assert rounding_stats(c.z1, tdt)[0] >= MIN_ROUNDED  # the stem map's rounding is part of the case
+    check_inputs(c.ref, tdt, "stem2")
+    got = run_stem2(device, dtype, stem_s, act, slope, c.x, c.ws, c.bs, c.wc, c.bc, cout)
+    assert_bits(got, expected(c.ref, tdt, lead=STEM_LEAD), f"stem2 s{stem_s} cout {cout} act {act} dtype {dtype}")
 
 
-@pytest.mark.parametrize('dtype', DT16)
-@pytest.mark.parametrize('n,h,w,cin', [(2, 7, 7, 128), (3, 10, 8, 256), (2, 7, 7, 512), (2, 10, 8, 128)])
-def test_exact_head_raw_store(device, n, h, w, cin, dtype):
-    """ycx_conv2d_head's raw-head store: cout 255 padded to 256, 64-pixel tiles straddling image
-    boundaries; conf_thres above 1 appends nothing, and the fp32 NCHW heads are the exact sums."""
-    o = operands(dtype, n, h, w, cin, 1, 1)
-    tdt, na, nc = TDT[dtype], 3, 80
-    cout = na * (nc + 5)
-    ref = o.z[:, :cout]
-    check_inputs(ref, torch.float32)
-    wp = torch.zeros(256, cin, dtype=tdt)
-    wp[:cout] = o.wt[:cout, :, 0, 0].to(tdt)
-    bp = torch.zeros(256)
-    bp[:cout] = o.b[:cout].float()
-    d = _desc_1x1(n, h, w, cin, cout, 256, o.in_extra, cin + o.in_extra, 0, cout, L.ACT_NONE, 0.0, dtype)
+HEAD = [(2, 7, 7, 128), (3, 10, 8, 256), (2, 7, 7, 512), (2, 10, 8, 128)]  # n, h, w, cin
+HEAD_NA, HEAD_NC = 3, 80
+HEAD_COUT = HEAD_NA * (HEAD_NC + 5)
+ROWS_SENTINEL = -7
+
+
+def head_descs(o):
+    d = _desc_1x1(o.n, o.h, o.w, o.cin, HEAD_COUT, 256, o.in_extra, o.x_full.shape[3], 0, HEAD_COUT, L.ACT_NONE, 0.0,
+                  o.dtype)
     d.out_layout = L.OUT_NCHW_F32
     hd = L.HeadDesc()
-    rows = na * h * w
-    hd.na, hd.no, hd.nc, hd.rows_total, hd.row_off, hd.conf_thres = na, nc + 5, nc, rows, 0, 2.0
-    for i in range(2 * na):
+    rows = HEAD_NA * o.h * o.w
+    hd.na, hd.no, hd.nc, hd.rows_total, hd.row_off, hd.conf_thres = HEAD_NA, HEAD_NC + 5, HEAD_NC, rows, 0, 2.0
+    for i in range(2 * HEAD_NA):
         hd.anchors_scaled[i] = 1.0 + i
-    xd, wd, bd = o.x_full.to(tdt).to(device), wp.to(device), bp.to(device)
-    heads = torch.zeros(n, cout, h, w, device=device)
-    cand = torch.zeros(n, rows, 8, device=device)
-    cand_rows = torch.zeros(n, rows, dtype=torch.int32, device=device)
-    counts = torch.zeros(n, dtype=torch.int32, device=device)
+    return d, hd
+
+
+@gpu
+@pytest.mark.parametrize('dtype', DT16)
+@pytest.mark.parametrize('n,h,w,cin', HEAD)
+def test_exact_head_raw_store(device, n, h, w, cin, dtype):
+    """ycx_conv2d_head's raw-head store: cout 255 padded to 256 (row 255 live), 64-pixel tiles straddling
+    image boundaries; conf_thres above 1 appends nothing, and the fp32 NCHW heads are the exact sums. The
+    heads buffer has no stride of its own: it, cand and cand_rows start as sentinels, heads lies between
+    sentinel guards, and nothing but heads may change."""
+    o = operands(dtype, n, h, w, cin, 1, 1)
+    tdt = TDT[dtype]
+    ref = o.z[:, :HEAD_COUT]
+    check_inputs(ref, torch.float32)
+    assert not bool((ref == SENTINEL_F32).any())
+    wp, bp = packed(o, HEAD_COUT, 256)
+    d, hd = head_descs(o)
+    rows = hd.rows_total
+    xd = guarded(o.x_full.to(tdt), input_guard(d, tdt.itemsize), device)
+    wd, bd = wp.reshape(256, cin).to(device), bp.to(device)
+    heads = guarded_out(torch.full((n, HEAD_COUT, h, w), SENTINEL_F32), device)
+    cand = torch.full((n, rows, 8), SENTINEL_F32, device=device)
+    cand_rows = torch.full((n, rows), ROWS_SENTINEL, dtype=torch.int32, device=device)
+    counts = torch.zeros(n, dtype=torch.int32, device=device)  # zeroed: the header's contract
     status = torch.zeros(1, dtype=torch.int32, device=device)
     L.check(L.lib.ycx_conv2d_head(ctypes.byref(d), ctypes.byref(hd), xd.data_ptr(), wd.data_ptr(), bd.data_ptr(),
                                   heads.data_ptr(), cand.data_ptr(), cand_rows.data_ptr(), counts.data_ptr(),
                                   status.data_ptr(), L.stream_handle(device)))
     torch.cuda.synchronize()
-    assert not counts.any() and not cand.any() and int(status) == 0
-    assert_bits(heads.cpu(), ref.float(), f"head cin {cin} {h}x{w} dtype {dtype}")
+    assert not counts.any() and int(status) == 0
+    assert bool((cand == SENTINEL_F32).all()) and bool((cand_rows == ROWS_SENTINEL).all())
+    what = f"head cin {cin} {h}x{w} dtype {dtype}"
+    assert_bits(fetch_out(heads, SENTINEL_F32, what=what), ref.float(), what)
 
 
 # ---- SiLU and pre-scaled SiLU at ulp level ----
@@ -551,12 +748,17 @@ def silu_conditions(z, act, tdt, what=""):
     return ref, excused, sub, share
 
 
-def check_silu(got, z, act, tdt, what, out_extra=16):
-    """got: the raw NHWC output buffer; z: the exact pre-activation NCHW (of the packed operands).
-    Elements are compared as values: +0 and -0 (silu(0) of either sign) coincide."""
+def check_silu(got, z, act, tdt, what, lead=OUT_LEAD, tail=OUT_TAIL):
+    """got: the raw framed NHWC output buffer (the slice at channel ``lead``, ``tail`` channels behind it,
+    the sentinel in both, bit for bit); z: the exact pre-activation NCHW (of the packed operands).
+    Elements of the slice are compared as values: +0 and -0 (silu(0) of either sign) coincide."""
     ref, excused, sub, share = silu_conditions(z, act, tdt, what)
-    assert not got[..., :out_extra].any(), "wrote outside the output channel slice"
-    g = got[..., out_extra:].contiguous()
+    c = ref.shape[3]
+    assert got.shape == (*ref.shape[:3], lead + c + tail) and got.dtype == tdt
+    frame = got.clone()
+    frame[..., lead:lead + c] = SENTINEL
+    assert_bits(frame, torch.full_like(got, SENTINEL), f"{what}: wrote outside the output channel slice")
+    g = got[..., lead:lead + c].contiguous()
     ulps = elt_ulps(g, rne(ref, tdt), tdt)
     if sub.any():  # fp16 subnormal results: an absolute bound, counted apart
         assert float((g.double() - ref).abs()[sub].max()) <= 2.0 ** -24, what
@@ -575,12 +777,14 @@ def silu_operands(dtype, n, h, w, cin, k, s, cout):
     return operands(dtype, n, h, w, cin, k, s, grid=(hx / 8, 1 / 8, hx, 1.0), cout=cout, seed=3)
 
 
+SILU_ACTS = [L.ACT_SILU, L.ACT_SILU_PS]
 SILU_CASES = [(3, 2, 13, 11, 64, 64, 3, 1, 0), (16, 2, 13, 11, 64, 128, 3, 1, 0), (18, 2, 13, 11, 64, 64, 3, 1, 0),
               (20, 2, 16, 16, 64, 128, 3, 1, 0), (22, 2, 13, 11, 64, 64, 1, 1, 0), (23, 2, 16, 16, 64, 64, 3, 1, 0),
               (50, 2, 32, 64, 64, 128, 3, 2, 0), (16, 2, 13, 11, 256, 128, 1, 1, 2)]  # last: the split-K reduce
 
 
-@pytest.mark.parametrize('act', [L.ACT_SILU, L.ACT_SILU_PS])
+@gpu
+@pytest.mark.parametrize('act', SILU_ACTS)
 @pytest.mark.parametrize('dtype', DT16)
 @pytest.mark.parametrize('tile,n,h,w,cin,cout,k,s,k_split', SILU_CASES)
 def test_silu_ulps(device, tile, n, h, w, cin, cout, k, s, k_split, dtype, act):
@@ -624,11 +828,12 @@ def stem2_silu_operands(act, dtype):
     return x, ws, bs, wc, bc, z2
 
 
-@pytest.mark.parametrize('act', [L.ACT_SILU, L.ACT_SILU_PS])
+@gpu
+@pytest.mark.parametrize('act', SILU_ACTS)
 @pytest.mark.parametrize('dtype', DT16)
 def test_silu_ulps_stem2(device, dtype, act):
     """stem2's two SiLU epilogues: the stem map must be RNE(silu) (any other element moves z2 by far
     more than an ulp), the output is held to the ulp bar."""
     x, ws, bs, wc, bc, z2 = stem2_silu_operands(act, dtype)
     got = run_stem2(device, dtype, 1, act, 0.0, x, ws, bs, wc, bc, 64)
-    check_silu(got, z2, act, TDT[dtype], f"stem2 dtype {dtype} act {act}", out_extra=8)
+    check_silu(got, z2, act, TDT[dtype], f"stem2 dtype {dtype} act {act}", lead=STEM_LEAD)

@@ -17,7 +17,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import make_model
+from helpers import SENTINEL, make_model
 from trio_case import YA_OFF, YB_OFF, YC_OFF, TrioCase
 from ycx import _lib as L
 from ycx.utils.synth import synthetic_images
@@ -55,7 +55,10 @@ def _ref_act(v, act):
 @pytest.mark.parametrize('shape,cin,cout_b,cout_c,acts,store_a', CASES)
 def test_conv2d_pair_pool(device, dtype, shape, cin, cout_b, cout_c, acts, store_a):
     """y2 and y3 (and y1 when stored) of the fused launch are bit-identical to ycx_conv2d_pair followed
-    by ycx_conv2d with in_pool = 1 on the stored y1; nothing is written outside the channel slices.
+    by ycx_conv2d with in_pool = 1 on the stored y1; nothing is written outside the channel slices: each
+    output is the interior slice of a sentinel-filled buffer, the sentinel must stand before and behind it
+    in the fused and in the unfused buffers (the padding rows of w_b / w_c are live), x lies between NaN
+    channels and NaN guards, and no output holds a NaN.
     On (3, 6, 96) y3 also agrees with a float64 conv of the max-pooled 16-bit y1, at
     test_conv2d_pair's tolerance (1e-2 bf16, 2e-3 fp16)."""
     case = TrioCase(device, dtype, shape, cin, cout_b, cout_c, acts)
@@ -66,21 +69,27 @@ def test_conv2d_pair_pool(device, dtype, shape, cin, cout_b, cout_c, acts, store
     if store_a:
         assert torch.equal(ya, ya0)
     else:
-        assert not ya.any()
-    assert not ya[..., :YA_OFF].any() and not yb[..., :YB_OFF].any() and not yc[..., :YC_OFF].any()
-    assert yc0[..., YC_OFF:].any()
+        assert bool((ya == SENTINEL).all())
+    for name, t, off, c in (('ya', ya, YA_OFF, 256), ('yb', yb, YB_OFF, cout_b), ('yc', yc, YC_OFF, cout_c),
+                            ('ya0', ya0, YA_OFF, 256), ('yb0', yb0, YB_OFF, cout_b), ('yc0', yc0, YC_OFF, cout_c)):
+        assert t.shape[3] > off + c, name  # a non-empty tail
+        assert bool((t[..., :off] == SENTINEL).all()) and bool((t[..., off + c:] == SENTINEL).all()), \
+            f"{name}: wrote outside the channel slice"
+        assert not bool(t.isnan().any()), f"{name}: something outside the operands reached the output"
+    body = yc0[..., YC_OFF:YC_OFF + cout_c]
+    assert bool((body != SENTINEL).any()) and bool((yb0[..., YB_OFF:YB_OFF + cout_b] != SENTINEL).any())
     if shape == S2:
         h = case.host
-        y1 = ya0[..., YA_OFF:].cpu().double().permute(0, 3, 1, 2)
+        y1 = ya0[..., YA_OFF:YA_OFF + 256].cpu().double().permute(0, 3, 1, 2)
         pre = F.conv2d(F.max_pool2d(y1, 2, 2), h['wc'][:cout_c].double()[:, :, None, None], h['bc'][:cout_c].double())
         ref = _ref_act(pre, acts[2]).permute(0, 2, 3, 1)
         tol = 1e-2 if dtype == L.DT_BF16 else 2e-3
-        torch.testing.assert_close(yc[..., YC_OFF:].cpu().double(), ref, rtol=tol, atol=tol)
+        torch.testing.assert_close(yc[..., YC_OFF:YC_OFF + cout_c].cpu().double(), ref, rtol=tol, atol=tol)
 
 
 def test_conv2d_pair_pool_rejects(device):
     """h odd, w % 32 != 0, c->in_pool == 0, c->cin != 256 and c->cout_pad != 128 are unsupported:
-    the status comes back before any launch (the outputs stay zero)."""
+    the status comes back before any launch (the outputs keep their sentinel)."""
     def edit(case, what):
         if what == 'h_odd':
             case.da.h = case.da.ho = case.db.h = case.db.ho = 3
@@ -100,7 +109,7 @@ def test_conv2d_pair_pool_rejects(device):
         ya, yb, yc = case.outputs()
         assert case.fused_status(ya, yb, yc) == L.YCX_ERR_UNSUPPORTED, what
         torch.cuda.synchronize()
-        assert not ya.any() and not yb.any() and not yc.any(), what
+        assert all(bool((t == SENTINEL).all()) for t in (ya, yb, yc)), what
 
 
 def _names(eng):

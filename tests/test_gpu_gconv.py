@@ -212,7 +212,6 @@ def test_grouped_silu_ulps(device, dtype, cin_g, k, s):
         ulps = elt_ulps(body, rne(ref, tdt), tdt).abs()
         print(f"\nfp32 grouped SiLU: max {int(ulps.max())} ulps")
         assert int(ulps.max()) <= 4
-    else:  # check_silu takes the raw buffer with the slice at the end and zeros before it
-        buf = torch.zeros(*body.shape[:3], 16 + o.C, dtype=tdt)
-        buf[..., 16:] = body
-        check_silu(buf, o.z, L.ACT_SILU, tdt, f"grouped SiLU dtype {dtype} cin_g {cin_g} k{k} s{s}")
+    else:  # check_silu takes the raw buffer: this file's frame (slice at 16, 8 behind it) is the dense file's
+        check_silu(got, o.z, L.ACT_SILU, tdt, f"grouped SiLU dtype {dtype} cin_g {cin_g} k{k} s{s}",
+                   lead=OUT_OFF, tail=EXTRA - OUT_OFF)

@@ -156,10 +156,8 @@ def check_silu_slice(got, o, cout, tdt, what):
         ulps = elt_ulps(body, rne(zz / (1 + torch.exp(-zz)), tdt), tdt).abs()
         print(f"\nfp32 SiLU {what}: max {int(ulps.max())} ulps")
         assert int(ulps.max()) <= 4
-    else:  # check_silu takes the raw buffer with the slice at the end and zeros before it
-        buf = torch.zeros(*body.shape[:3], 16 + cout, dtype=tdt)
-        buf[..., 16:] = body
-        check_silu(buf, o.z, L.ACT_SILU, tdt, what)
+    else:  # check_silu takes the raw framed buffer and holds the sentinel around the slice to its bits too
+        check_silu(got, o.z, L.ACT_SILU, tdt, what, lead=OUT_OFF, tail=got.shape[3] - OUT_OFF - cout)
 
 
 @pytest.mark.gpu

@@ -9,7 +9,13 @@ The reference is torch's float64 conv2d over reorg(x), reorg being four strided 
 need rounding and >= 1 % are ties; the fp32 case that the cast is lossless.
 
 Shapes (reorganised maps, n = 2): 9 x 11 (every border, a ragged pixel tail), 16 x 32, 8 x 64 (a full
-MFMA row); stride 1 and 2; cout 32 and 64, 48 padded to 64; C = 3 and 1; output channel slice at 8."""
+MFMA row); stride 1 and 2; cout 32 and 64, 48 padded to 64; C = 3 and 1.
+
+The frame of the exact files (tests/helpers.py): the output slice lies at channel 8 of a sentinel-filled
+buffer 8 + cout + 8 wide, itself between sentinel guards, and whole buffers are compared; the fp32 image
+lies between NaN guards of (2 * 2w + 2 + 1) floats (the 6x6 / pad-2 view of the conv) inside one
+allocation; the padding rows of cout 48 in 64 are the operands' own channels 48 .. 63, not zeros.
+tests/test_conv_exact_plan.py walks the tables below without a GPU."""
 import ctypes
 import functools
 import types
@@ -18,18 +24,21 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from helpers import dyadic, elt_neighbours, elt_ulps, rne, rounding_stats
+from helpers import (OUT_TAIL, SENTINEL, assert_bits, dyadic, elt_neighbours, elt_ulps, expected_frame, fetch_out,
+                     guard_elems, guarded, guarded_out, out_frame, rne, rounding_stats)
+from ycx import _lib as L  # a missing library is an error, on the CPU too (tests/test_conv_exact_plan.py)
 
-pytestmark = pytest.mark.gpu
-
-L = pytest.importorskip("ycx._lib")
+gpu = pytest.mark.gpu  # every test here; the tables and builders import without a device
 
 TDT = {L.DT_BF16: torch.bfloat16, L.DT_F16: torch.float16, L.DT_F32: torch.float32}
 SPAN = 1 << 20
 MIN_ROUNDED, MIN_TIES = 0.10, 0.01
 ACTS = [(L.ACT_NONE, 0.0), (L.ACT_LEAKY, 0.125), (L.ACT_LEAKY, 0.25)]
 X_MAX, X_STEP, W_MAX, W_STEP, B_MAX, B_STEP = 4.0, 1 / 32, 2.0, 1 / 32, 2.0, 1 / 16
-OUT_EXTRA = 8
+OUT_EXTRA = 8  # the slice's channel offset; OUT_TAIL sentinel channels follow it
+DTYPES = [L.DT_BF16, L.DT_F16, L.DT_F32]
+COUTS = [32, 64]
+BELOW_PAD = (48, 64)  # cout, cout_pad
 SHAPES = [(9, 11), (16, 32), (8, 64)]
 assert 108 * (X_MAX / X_STEP) * (W_MAX / W_STEP) == 884736 < SPAN
 
@@ -69,38 +78,49 @@ def check_inputs(ref64, tdt, what=""):
         f"{what}: inputs too easy, {rounded:.3f} of the outputs need rounding, {ties:.3f} are ties"
 
 
-def assert_bits(got, exp, what=""):
-    it = torch.int32 if got.dtype == torch.float32 else torch.int16
-    assert got.shape == exp.shape and got.dtype == exp.dtype
-    if torch.equal(got.contiguous().view(it), exp.contiguous().view(it)):
-        return
-    bad = got.contiguous().view(it) != exp.contiguous().view(it)
-    d = elt_ulps(got, exp, got.dtype)[bad]
-    raise AssertionError(f"{what}: {int(bad.sum())} of {bad.numel()} elements differ from RNE(true sum); "
-                         f"distance in representable values: min {int(d.min())}, max {int(d.max())}; "
-                         f"first at {[int(v) for v in bad.nonzero()[0]]}")
-
-
 def cpad_of(cout, dtype):
     return -(-cout // 64) * 64 if dtype == L.DT_F32 else (32 if cout <= 32 else -(-cout // 64) * 64)
 
 
-def launch(device, o, dtype, cout, act=L.ACT_NONE, slope=0.0, cpad=None, out_scale=1.0, via_ops=False):
-    """One call through the C ABI (or as a YCX_OP_STEM_REORG through ycx_run_ops); the raw output buffer."""
-    cpad = cpad or cpad_of(cout, dtype)
-    wp = torch.zeros(3, 3, 4 * o.c, cpad)
-    wp[..., :cout] = o.wt[:cout].permute(2, 3, 1, 0).float()
-    bp = torch.zeros(cpad)
-    bp[:cout] = o.b[:cout].float()
-    ydt = torch.uint8 if dtype == L.DT_FP8 else TDT[dtype]
+def packed(o, cout, cpad):
+    """fp32 weights [3][3][4C][cpad] and bias [cpad]: the padding channels cout .. cpad are the operands' own."""
+    assert cpad <= o.wt.shape[0]
+    assert cpad == cout or bool(o.wt[cout:cpad].flatten(1).any(1).all())  # no padding row is zero
+    return o.wt[:cpad].permute(2, 3, 1, 0).contiguous().float(), o.b[:cpad].float()
+
+
+def desc_of(o, dtype, cout, act=L.ACT_NONE, slope=0.0, cpad=None, out_scale=1.0):
+    """The ycx_stem_conv_reorg descriptor of one case (no device)."""
     d = L.ConvDesc()
     d.n, d.h, d.w, d.cin, d.in_c_off, d.in_c_stride = o.n, o.h, o.w, 4 * o.c, 0, o.c
-    d.ho, d.wo, d.cout, d.cout_pad, d.out_c_off, d.out_c_stride = o.ho, o.wo, cout, cpad, OUT_EXTRA, cout + OUT_EXTRA
+    d.ho, d.wo, d.cout, d.cout_pad = o.ho, o.wo, cout, cpad or cpad_of(cout, dtype)
+    d.out_c_off, d.out_c_stride = OUT_EXTRA, OUT_EXTRA + cout + OUT_TAIL
     d.kh = d.kw = 3
     d.stride, d.pad, d.act, d.leaky_slope, d.dtype, d.out_layout = o.s, 1, act, slope, dtype, L.OUT_NHWC
     d.out_scale = out_scale
-    xd, wd, bd = o.x.float().to(device), wp.to(device), bp.to(device)
-    yd = torch.zeros(o.n, o.ho, o.wo, cout + OUT_EXTRA, dtype=ydt, device=device)
+    return d
+
+
+def image_guard(o):
+    """Guard floats of the [n][C][2h][2w] image: the conv is a 6x6 / pad-2 conv over it (16-byte aligned
+    behind the guard; the kernel asks for 8)."""
+    return guard_elems(2, 2 * o.w, 1, 4)
+
+
+E4M3 = torch.float8_e4m3fn
+SENTINEL_BYTE = int(torch.tensor(SENTINEL).to(E4M3).view(torch.uint8))  # the e4m3 code of the sentinel
+
+
+def launch(device, o, dtype, cout, act=L.ACT_NONE, slope=0.0, cpad=None, out_scale=1.0, via_ops=False):
+    """One call through the C ABI (or as a YCX_OP_STEM_REORG through ycx_run_ops); the raw output buffer."""
+    d = desc_of(o, dtype, cout, act, slope, cpad, out_scale)
+    wp, bp = packed(o, cout, d.cout_pad)
+    if dtype == L.DT_FP8:
+        y, sentinel = torch.full((o.n, o.ho, o.wo, d.out_c_stride), SENTINEL_BYTE, dtype=torch.uint8), SENTINEL_BYTE
+    else:
+        y, sentinel = out_frame(o.n, o.ho, o.wo, cout, TDT[dtype], OUT_EXTRA), SENTINEL
+    xd, wd, bd = guarded(o.x.float(), image_guard(o), device), wp.to(device), bp.to(device)
+    yd = guarded_out(y, device)
     st = L.stream_handle(device)
     if via_ops:
         op = L.Op()
@@ -112,14 +132,12 @@ def launch(device, o, dtype, cout, act=L.ACT_NONE, slope=0.0, cpad=None, out_sca
         L.check(L.lib.ycx_stem_conv_reorg(ctypes.byref(d), xd.data_ptr(), wd.data_ptr(), bd.data_ptr(),
                                           yd.data_ptr(), st), "ycx_stem_conv_reorg")
     torch.cuda.synchronize()
-    return yd.cpu()
+    return fetch_out(yd, sentinel, what="stem_reorg")
 
 
 def expected(ref64, tdt):
-    r = ref64.permute(0, 2, 3, 1)
-    exp = torch.zeros(*r.shape[:3], r.shape[3] + OUT_EXTRA, dtype=tdt)
-    exp[..., OUT_EXTRA:] = rne(r, tdt)
-    return exp
+    """The whole output buffer: RNE(ref) in the channel slice, the sentinel outside it."""
+    return expected_frame(rne(ref64.permute(0, 2, 3, 1), tdt), OUT_EXTRA)
 
 
 def run_acts(device, o, dtype, cout, what, cpad=None):
@@ -131,28 +149,33 @@ def run_acts(device, o, dtype, cout, what, cpad=None):
         assert_bits(got, expected(ref, tdt), f"{what} act {act} slope {slope}")
 
 
-@pytest.mark.parametrize('dtype', [L.DT_BF16, L.DT_F16, L.DT_F32])
-@pytest.mark.parametrize('cout', [32, 64])
+@gpu
+@pytest.mark.parametrize('dtype', DTYPES)
+@pytest.mark.parametrize('cout', COUTS)
 @pytest.mark.parametrize('s', [1, 2])
 @pytest.mark.parametrize('h,w', SHAPES)
 def test_exact_stem_reorg(device, h, w, s, cout, dtype):
     run_acts(device, operands(h, w, s), dtype, cout, f"stem_reorg {h}x{w} s{s} cout {cout} dtype {dtype}")
 
 
-@pytest.mark.parametrize('dtype', [L.DT_BF16, L.DT_F16, L.DT_F32])
+@gpu
+@pytest.mark.parametrize('dtype', DTYPES)
 def test_exact_stem_reorg_cout_below_pad(device, dtype):
-    """cout 48 in a 64-channel pad: channels 48..63 of the pad are computed and never stored."""
-    run_acts(device, operands(9, 11, 1), dtype, 48, f"stem_reorg cout 48/64 dtype {dtype}", cpad=64)
+    """cout 48 in a 64-channel pad: channels 48..63 of the pad are computed on live rows and never stored."""
+    cout, cpad = BELOW_PAD
+    run_acts(device, operands(9, 11, 1), dtype, cout, f"stem_reorg cout {cout}/{cpad} dtype {dtype}", cpad=cpad)
 
 
-@pytest.mark.parametrize('dtype', [L.DT_BF16, L.DT_F16, L.DT_F32])
+@gpu
+@pytest.mark.parametrize('dtype', DTYPES)
 @pytest.mark.parametrize('s', [1, 2])
 def test_exact_stem_reorg_one_channel(device, s, dtype):
     """C = 1 (a grey image): 4 reorganised channels, K = 36 in two MFMA steps."""
     run_acts(device, operands(9, 11, s, c=1), dtype, 32, f"stem_reorg C1 s{s} dtype {dtype}")
 
 
-@pytest.mark.parametrize('dtype', [L.DT_BF16, L.DT_F16, L.DT_F32])
+@gpu
+@pytest.mark.parametrize('dtype', DTYPES)
 @pytest.mark.parametrize('s', [1, 2])
 def test_op_stem_reorg_matches_direct_call(device, s, dtype):
     o = operands(9, 11, s)
@@ -165,19 +188,20 @@ def test_op_stem_reorg_matches_direct_call(device, s, dtype):
 
 # ---- e4m3 store: bit-exact (tests/test_gpu_fp8_exact.py): the operands are exact, the fp32 value is cast
 # straight to e4m3, so every byte is torch's cast of clamp(ref * out_scale, +-448) ----
-E4M3 = torch.float8_e4m3fn
+FP8_CASES = [(9, 11, 64), (8, 64, 32)]
 
 
+@gpu
 @pytest.mark.parametrize('s', [1, 2])
-@pytest.mark.parametrize('h,w,cout', [(9, 11, 64), (8, 64, 32)])
+@pytest.mark.parametrize('h,w,cout', FP8_CASES)
 def test_stem_reorg_fp8_store(device, h, w, cout, s):
     o = operands(h, w, s)
     so = 4.0  # where |z| passes 112 the +-448 clamp is exercised too
     for act, slope in ACTS[:2]:
         ref = apply_act(o.z[:, :cout], act, slope).permute(0, 2, 3, 1)
         got = launch(device, o, L.DT_FP8, cout, act, slope, out_scale=so)
-        exp = torch.zeros_like(got)
-        exp[..., OUT_EXTRA:] = rne((ref * so).clamp(-448.0, 448.0), E4M3).view(torch.uint8)
+        exp = torch.full_like(got, SENTINEL_BYTE)
+        exp[..., OUT_EXTRA:OUT_EXTRA + cout] = rne((ref * so).clamp(-448.0, 448.0), E4M3).view(torch.uint8)
         bad = got != exp
         assert not bad.any(), f"stem_reorg fp8 {h}x{w} s{s} act {act}: {int(bad.sum())} of {bad.numel()} bytes differ " \
                               f"from e4m3(clamp(ref * so)); first at {[int(v) for v in bad.nonzero()[0]]}"
@@ -195,9 +219,9 @@ def silu_ref(z, act):
     return z / (1 + torch.exp(-z))
 
 
-def check_silu(got, z, act, tdt, what):
-    """Bit-exact where the float64 reference lies farther than (|z| + 8) 2^-23 relative from a rounding
-    boundary, within one element-ulp of RNE(reference) everywhere (fp16 subnormals: 2^-24 absolute)."""
+def silu_conditions(z, act, tdt, what):
+    """The input conditions of a SiLU case, from the reference alone: the NHWC reference, the excused
+    elements, the fp16 subnormal results."""
     assert float(z.abs().max()) <= SILU_MAX_Z, "input condition: |z| <= 32"
     zz = z.permute(0, 2, 3, 1).contiguous()
     ref = silu_ref(zz, act)
@@ -207,8 +231,18 @@ def check_silu(got, z, act, tdt, what):
     sub = (ref.abs() < 2.0 ** -14) if tdt == torch.float16 else torch.zeros_like(excused)
     share = float((excused & ~sub).double().mean())
     assert share <= MAX_EXCUSED[tdt], f"{what}: input condition, {share:.4f} of the elements are excused"
-    assert not got[..., :OUT_EXTRA].any(), "wrote outside the output channel slice"
-    g = got[..., OUT_EXTRA:].contiguous()
+    return ref, excused, sub, share
+
+
+def check_silu(got, z, act, tdt, what):
+    """Bit-exact where the float64 reference lies farther than (|z| + 8) 2^-23 relative from a rounding
+    boundary, within one element-ulp of RNE(reference) everywhere (fp16 subnormals: 2^-24 absolute)."""
+    ref, excused, sub, share = silu_conditions(z, act, tdt, what)
+    c = ref.shape[3]
+    frame = got.clone()
+    frame[..., OUT_EXTRA:OUT_EXTRA + c] = SENTINEL
+    assert_bits(frame, torch.full_like(got, SENTINEL), f"{what}: wrote outside the output channel slice")
+    g = got[..., OUT_EXTRA:OUT_EXTRA + c].contiguous()
     ulps = elt_ulps(g, rne(ref, tdt), tdt)
     if sub.any():
         assert float((g.double() - ref).abs()[sub].max()) <= 2.0 ** -24, what
@@ -219,12 +253,16 @@ def check_silu(got, z, act, tdt, what):
                           f"boundary differ from RNE(ref) ({share:.4f} excused, {int(sub.sum())} subnormal)"
 
 
+SILU_GRID = (1 / 8, 1 / 8, 1.0, 1.0, 1.0)
+
+
+@gpu
 @pytest.mark.parametrize('act', [L.ACT_SILU, L.ACT_SILU_PS])
 @pytest.mark.parametrize('dtype', [L.DT_BF16, L.DT_F16])
 @pytest.mark.parametrize('s', [1, 2])
 def test_silu_ulps_stem_reorg(device, s, dtype, act):
     """x and w in 1/8 steps within +-1 (K = 108: hx = 2^floor(log2(12 / sqrt(K))) = 1), bias in 1/16 steps
     within +-1: z of a few units. YCX_ACT_SILU_PS: the weights and bias themselves are on the grid."""
-    o = operands(9, 11, s, grid=(1 / 8, 1 / 8, 1.0, 1.0, 1.0), seed=3)
+    o = operands(9, 11, s, grid=SILU_GRID, seed=3)
     got = launch(device, o, dtype, 64, act, 0.0)
     check_silu(got, o.z, act, TDT[dtype], f"stem_reorg s{s} dtype {dtype} act {act}")

@@ -120,6 +120,70 @@ def test_exact_comparator_bites(dtype_name):
     assert int(bad_d[neg].sum()) >= 0.9 * int(neg.sum()) and not bad_d[~neg].any()
 
 
+@pytest.mark.parametrize('dtype_name', ['bfloat16', 'float16'])
+def test_framed_comparator_bites(dtype_name):
+    """The framed whole-buffer comparison of tests/test_gpu_conv_exact.py (helpers: sentinel-filled buffer,
+    slice in its interior, live padding rows) on a synthetic result. Each of these must fail it:
+    (a) a padding channel stored after the slice, (b) a zero stored into the lead, (c) one unwritten
+    element whose true value is 0, (d) an fp32 NCHW plane block written one plane late. And (a)-(c) pass
+    the comparison the file used before -- a zero-filled buffer with the slice as its last channels and
+    zero padding rows, where a stored padding channel is act(0) = 0 in the next pixel's lead: the gap the
+    frame closes, shown without running a wrong kernel."""
+    import torch
+    from helpers import (OUT_LEAD, OUT_TAIL, SENTINEL, assert_bits, dyadic, expected_frame, expected_planes,
+                         live_padding_share, out_frame, out_planes, rne)
+    tdt = getattr(torch, dtype_name)
+    n, h, w, cout, cpad = 2, 5, 3, 24, 32
+    g = torch.Generator().manual_seed(1)
+    z = dyadic((n, h, w, cpad), -8, 8, 1 / 16, g)  # NHWC "true sums" of all cpad channels, padding rows live
+    z[1, 2, 1, 5] = 0.0                            # a true value of 0 does occur on these grids
+    ref, pad = rne(z[..., :cout], tdt), rne(z[..., cout:], tdt)
+    live_padding_share(pad, SENTINEL)
+
+    def fails(got, exp):
+        try:
+            assert_bits(got, exp, "synthetic")
+        except AssertionError:
+            return True
+        return False
+
+    def old_frame(elems):  # the earlier convention: zeros, the slice at the end, nothing behind it
+        buf = torch.zeros(n, h, w, OUT_LEAD + cout, dtype=tdt)
+        buf[..., OUT_LEAD:] = elems
+        return buf
+
+    new_exp, old_exp = expected_frame(ref), old_frame(ref)
+    assert not fails(expected_frame(ref), new_exp) and not fails(old_frame(ref), old_exp)
+    # (a) the first padding channel stored too: in the new frame its live value lands on the tail; in the old
+    #     one a zero row's act(0) = 0 lands on channel 0 of the next pixel's (zero) lead
+    got = expected_frame(ref)
+    got[..., OUT_LEAD + cout] = pad[..., 0]
+    assert fails(got, new_exp)
+    old = old_frame(ref).reshape(-1, OUT_LEAD + cout)
+    old[1:, 0] = 0.0  # pixel p's spill is pixel p + 1's channel 0 (the last pixel's leaves the buffer)
+    assert not fails(old.reshape(old_exp.shape), old_exp)
+    # (b) a zero stored into the lead
+    got = expected_frame(ref)
+    got[0, 1, 2, 3] = 0.0
+    assert fails(got, new_exp)
+    old = old_frame(ref)
+    old[0, 1, 2, 3] = 0.0
+    assert not fails(old, old_exp)
+    # (c) one element never written, its true value 0: the sentinel still stands there; a zero-filled buffer agrees
+    got = expected_frame(ref)
+    got[1, 2, 1, OUT_LEAD + 5] = SENTINEL
+    assert fails(got, new_exp)
+    old = old_frame(ref)
+    old[1, 2, 1, OUT_LEAD + 5] = 0.0  # what torch.zeros left there
+    assert not fails(old, old_exp)
+    assert out_frame(n, h, w, cout, tdt).shape[3] == OUT_LEAD + cout + OUT_TAIL
+    # (d) fp32 NCHW: every plane one plane late (out_c_off 2 where the descriptor says 1)
+    r32 = z[..., :cout].permute(0, 3, 1, 2).float()
+    late = out_planes(n, cout, h, w)  # [n][cout + 2][h][w]: the last plane lands on the trailing sentinel plane
+    late[:, 2:cout + 2] = r32
+    assert fails(late, expected_planes(r32)) and not fails(expected_planes(r32), expected_planes(r32))
+
+
 def test_exact_comparator_bites_e4m3():
     """The comparator of tests/test_gpu_fp8_exact.py (whole byte buffers against torch's e4m3fn cast of the
     clamped float64 reference) on one of its cases (tile 35, cin 64, 3x3, act none, both output scales):
