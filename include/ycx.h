@@ -17,6 +17,8 @@
  *                       dw_conv                                 nets/common.py:20-22
  *                       RobustConv2's strided depthwise half     nets/common.py:132
  *   ycx_deconv2d        nn.ConvTranspose2d, kernel == stride     nets/common.py:133-134 (RobustConv2)
+ *   ycx_ghost_dw        GhostConv's cat[y, cv2(y)], cv2 depthwise 5x5  nets/common.py:142-152
+ *                       Ghost's conv(x) + shortcut(x) on that concat   nets/common.py:233-245
  *   ycx_stem_conv       first Conv on the fp32 NCHW image       nets/common.py:105-106 (Cin=3)
  *   ycx_stem_conv2      first two Convs fused (3->32, then 3x3   cfg/net/yolov7.yaml:7-8,
  *                       stride 2 -> 64); the stem output stays   nets/common.py:97-109
@@ -48,7 +50,8 @@ extern "C" {
 #endif
 
 /* The version stays 9 across the `groups` field appended to ycx_conv_desc (and the
- * ycx_conv2d_grouped / YCX_OP_GCONV additions) and across ycx_deconv2d / YCX_OP_DECONV, which add
+ * ycx_conv2d_grouped / YCX_OP_GCONV additions) and across ycx_deconv2d / YCX_OP_DECONV and
+ * ycx_ghost_dw / YCX_OP_GHOST, which each add
  * an entry point and an op kind but no struct and no field: the library and its ctypes mirror
  * (ycx/_lib.py) are always built together in-tree and check each other's struct sizes
  * (ycx_struct_size, ids 0 to 11 unchanged) at load time; a zero-initialised descriptor
@@ -249,7 +252,8 @@ enum { YCX_OP_CONV = 1, YCX_OP_STEM = 2, YCX_OP_POOL = 3, YCX_OP_COPY = 4, YCX_O
        YCX_OP_CONV_PAIR = 7,
        YCX_OP_STEM_REORG = 8 /* ycx_stem_conv_reorg: d.conv, in, weight, bias, out */,
        YCX_OP_GCONV = 9 /* ycx_conv2d_grouped: d.conv, in, weight (fp32), bias, out, residual */,
-       YCX_OP_DECONV = 10 /* ycx_deconv2d: d.conv, in, weight, bias, out */ };
+       YCX_OP_DECONV = 10 /* ycx_deconv2d: d.conv, in, weight, bias, out */,
+       YCX_OP_GHOST = 11 /* ycx_ghost_dw: d.conv, in, weight (fp32), bias, out, residual */ };
 typedef struct ycx_op {
   int32_t kind;
   int32_t pad_;
@@ -342,6 +346,28 @@ ycx_status ycx_conv2d_grouped(const ycx_conv_desc* d, const void* x, const float
  * before the data pointers, as in ycx_conv2d_grouped. */
 ycx_status ycx_deconv2d(const ycx_conv_desc* d, const void* x, const void* w, const float* bias, void* y,
                         void* stream);
+/* GhostConv's output cat[y, cv2(y)] (nets/common.py:150-152), cv2 the depthwise 5x5 / stride 1 / pad 2
+ * conv every GhostConv has, optionally plus Ghost's shortcut (:244-245) over all 2c channels:
+ *   out[.., j]     = x[.., j] (+ res[.., j])                                                   j < c
+ *   out[.., c + j] = act(bias[j] + sum_ky sum_kx w[ky][kx][j] * x[n][oy + ky - 2][ox + kx - 2][j]) (+ res[.., c + j])
+ * d: cin = c (the hidden map), cout = 2c, groups = c, kh == kw == 5, stride 1, pad 2, ho == h, wo == w;
+ * dtype bf16 / fp16 / f32, YCX_OUT_NHWC; cout_pad and tile are not used. x, y, residual: NHWC channel
+ * slices (in_c_*, out_c_*, res_c_*; c, offsets and strides multiples of 8); the output and residual
+ * slices are 2c wide. w: fp32 [5][5][c], the bytes of ycx_conv2d_grouped's [kh][kw][cout][1], unscaled;
+ * bias: fp32 [c].
+ * The first half without a residual is a bit copy; with one, an fp32 add rounded once to the element
+ * type (nearest even). The second half accumulates in fp32, one fmaf per tap in the order kernel row,
+ * kernel column, taps outside the image adding zero: the order of ycx_conv2d_grouped, so on finite
+ * operands it is bit-identical to that kernel. act YCX_ACT_NONE / SILU (plain) / LEAKY.
+ * In place: x == y with in_c_off == out_c_off and in_c_stride == out_c_stride means the first half
+ * already sits where it belongs; only the second half is stored. In place with a residual, or x == y
+ * with any other intersecting channel ranges: YCX_ERR_BAD_ARG.
+ * YCX_ERR_BAD_ARG before any device call: null pointers, inconsistent shapes (ho / wo), a slice past its
+ * stride. YCX_ERR_UNSUPPORTED: any other k, stride, pad or groups, cout != 2 cin, fp8, YCX_ACT_SILU_PS,
+ * in_pool, k_split > 1, another out_layout, a channel field that is no multiple of 8. The descriptor is
+ * judged before the data pointers, as in ycx_conv2d_grouped. */
+ycx_status ycx_ghost_dw(const ycx_conv_desc* d, const void* x, const float* w, const float* bias, void* y,
+                        const void* residual, void* stream);
 /* ycx_conv2d with a caller-owned workspace for d->k_split > 1 (split-K: fp32 partials of
  * every K range, then one reduce launch; ycx_conv2d itself returns YCX_ERR_CAPACITY for
  * k_split > 1). ycx_conv_workspace_size: the bytes it needs (0 without a split). */

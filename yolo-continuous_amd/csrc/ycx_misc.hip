@@ -439,6 +439,8 @@ static ycx_status run_one(const ycx_op& op, void* stream) {
                                 stream);
     case YCX_OP_DECONV:
       return ycx_deconv2d(&op.d.conv, op.in, op.weight, op.bias, op.out, stream);
+    case YCX_OP_GHOST:
+      return ycx_ghost_dw(&op.d.conv, op.in, (const float*)op.weight, op.bias, op.out, op.residual, stream);
     case YCX_OP_POOL:
       return ycx_maxpool(&op.d.pool, op.in, op.out, stream);
     case YCX_OP_COPY:
@@ -491,11 +493,12 @@ extern "C" ycx_status ycx_set_trace(int32_t on) {
 
 static void trace_push(int32_t i, const ycx_op& op) {
   static const char* kinds[] = {"?", "conv", "stem", "pool", "copy", "stem2", "head", "conv_pair", "stem_reorg",
-                                "gconv", "deconv"};
-  const char* k = (op.kind >= 1 && op.kind <= 10) ? kinds[op.kind] : kinds[0];
+                                "gconv", "deconv", "ghost"};
+  const char* k = (op.kind >= 1 && op.kind <= 11) ? kinds[op.kind] : kinds[0];
   char buf[160];
   if (op.kind == YCX_OP_CONV || op.kind == YCX_OP_STEM || op.kind == YCX_OP_HEAD || op.kind == YCX_OP_STEM2 ||
-      op.kind == YCX_OP_CONV_PAIR || op.kind == YCX_OP_STEM_REORG || op.kind == YCX_OP_GCONV || op.kind == YCX_OP_DECONV) {
+      op.kind == YCX_OP_CONV_PAIR || op.kind == YCX_OP_STEM_REORG || op.kind == YCX_OP_GCONV || op.kind == YCX_OP_DECONV ||
+      op.kind == YCX_OP_GHOST) {
     const ycx_conv_desc& c = op.kind == YCX_OP_HEAD ? op.d.head.conv
                              : op.kind == YCX_OP_STEM2 || op.kind == YCX_OP_CONV_PAIR ? op.d.pair[1] : op.d.conv;
     snprintf(buf, sizeof buf, "op%d %s %s n%d %dx%d %d->%d k%d s%d", i, k,

@@ -29,6 +29,7 @@ OUT_NHWC, OUT_NCHW_F32, OUT_NHWC_UP2 = 0, 1, 2
 OP_CONV, OP_STEM, OP_POOL, OP_COPY, OP_STEM2, OP_HEAD, OP_CONV_PAIR, OP_STEM_REORG = 1, 2, 3, 4, 5, 6, 7, 8
 OP_GCONV = 9
 OP_DECONV = 10
+OP_GHOST = 11
 
 _i32 = ctypes.c_int32
 
@@ -129,6 +130,7 @@ _SIGS = [
     ("ycx_conv2d", _i32, [ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _VP, _VP, _VP]),
     ("ycx_conv2d_grouped", _i32, [ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _VP, _VP, _VP]),
     ("ycx_deconv2d", _i32, [ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _VP, _VP]),
+    ("ycx_ghost_dw", _i32, [ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _VP, _VP, _VP]),
     ("ycx_conv_workspace_size", ctypes.c_size_t, [ctypes.POINTER(ConvDesc)]),
     ("ycx_conv2d_ws", _i32, [ctypes.POINTER(ConvDesc), _VP, _VP, _VP, _VP, _VP, _VP, ctypes.c_size_t, _VP]),
     ("ycx_conv_pick_ksplit", _i32, [ctypes.POINTER(ConvDesc)]),

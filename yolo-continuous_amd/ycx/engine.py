@@ -7,8 +7,8 @@ Lowering (once per input shape / device / precision):
    each module into graph nodes — conv (BN folded, RepConv re-parameterised,
    Bottleneck residual fused into the epilogue), stem conv (first conv on the
    fp32 NCHW image; ``stem_reorg`` when ReOrg precedes it: the space-to-depth is folded into
-   that conv's operand gather), grouped conv, transposed conv (kernel == stride: ``deconv``), max-pool,
-   upsample, concat, Detect/IDetect heads.
+   that conv's operand gather), grouped conv, transposed conv (kernel == stride: ``deconv``), GhostConv's
+   depthwise 5x5 + concat with Ghost's shortcut (``ghost``), max-pool, upsample, concat, Detect/IDetect heads.
 2. Passes: nearest-x2 upsample fused into its producing conv's store
    (YCX_OUT_NHWC_UP2); the SPPCSPC 5/9/13 pools run as a k5 cascade (exact for
    max with -inf padding); every concat input that a kernel produces is written
@@ -33,7 +33,7 @@ from torch import nn
 
 from . import _lib as L
 from .nets.common import (SP, SPP, SPPCSPC, SPPF, MP, Bottleneck, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC,
-                          Concat, Conv, DownC, ReOrg, RepConv, Res, RobustConv, RobustConv2)
+                          Concat, Conv, DownC, Ghost, GhostConv, ReOrg, RepConv, Res, RobustConv, RobustConv2)
 from .nets.detect import Detect, IAuxDetect, IDetect
 from .schedule import Schedule, cascade_fits, cout_pad  # noqa: F401  (cascade_fits: re-exported)
 
@@ -197,6 +197,27 @@ class Graph:
         return self.add('deconv', [x], Val(x.n, ho, wo, cout), w=w64, b=b64, k=s, s=s, p=0, act=act[0], slope=act[1],
                         residual=None, ho=ho, wo=wo, layout=L.OUT_NHWC)
 
+    def ghost(self, y: Val, w64, b64, act=(L.ACT_NONE, 0.0), residual=None):
+        """GhostConv's cat[y, cv2(y)] (+ residual over all 2c channels) as a node of its own kind, 'ghost'
+        (ycx_ghost_dw); w64 [c][1][5][5] is cv2's folded depthwise 5x5 / s1 / p2 weight. Like 'gconv' and
+        'deconv', no conv-fusing pass looks at it; the concat-slice aliasing takes it, and a residual-free
+        one gets y placed in the first half of its own output (``Plan._passes``)."""
+        c = int(w64.shape[0])
+        if y.role in ('input', 'reorg'):
+            raise NotImplementedError("ycx: GhostConv on the model input")
+        if tuple(w64.shape) != (y.c, 1, 5, 5):
+            raise NotImplementedError(f"ycx: ghost conv weight {tuple(w64.shape)} on {y.c} channels: ycx_ghost_dw takes "
+                                      f"a depthwise 5x5 over the hidden map")
+        if c % 8:
+            raise NotImplementedError(f"ycx: ghost conv on {c} hidden channels: ycx_ghost_dw takes c % 8 == 0 "
+                                      f"(a GhostConv of c2 % 16 == 0)")
+        if residual is not None and (residual.n, residual.h, residual.w, residual.c) != (y.n, y.h, y.w, 2 * c):
+            raise ValueError(f"ycx: Ghost shortcut of shape {(residual.n, residual.h, residual.w, residual.c)} "
+                             f"on an output of {(y.n, y.h, y.w, 2 * c)}")
+        ins = [y] + ([residual] if residual is not None else [])
+        return self.add('ghost', ins, Val(y.n, y.h, y.w, 2 * c), w=w64, b=b64, k=5, s=1, p=2, act=act[0],
+                        slope=act[1], residual=residual, ho=y.h, wo=y.w, layout=L.OUT_NHWC, groups=c)
+
     def pool(self, x: Val, k, s, p):
         if x.role == 'input':
             raise NotImplementedError("ycx: pooling the raw input image")
@@ -231,6 +252,45 @@ def conv_module(g: Graph, m: Conv, x: Val, residual=None):
     w, b = fold_bn(c.weight, m.bn)
     return g.conv(x, w, b, _square(c.kernel_size, 'kernel'), _square(c.stride, 'stride'),
                   _square(c.padding, 'padding'), act_of(m.act), residual=residual, groups=int(c.groups))
+
+
+def ghostconv_module(g: Graph, m: GhostConv, x: Val, residual=None):
+    """GhostConv (nets/common.py:142-152): cv1 as an ordinary conv / gconv node, then one 'ghost' node for
+    cv2, the concat and, for the second GhostConv of a Ghost block, the shortcut."""
+    c = m.cv2.conv
+    k, s, p = _square(c.kernel_size, 'kernel'), _square(c.stride, 'stride'), _square(c.padding, 'padding')
+    if not (k == 5 and s == 1 and p == 2 and c.groups == c.in_channels == c.out_channels
+            and _pair(c.dilation) == (1, 1)):
+        raise NotImplementedError(f"ycx: GhostConv.cv2 with k {k}, s {s}, p {p}, groups {c.groups} on "
+                                  f"{c.in_channels} -> {c.out_channels} channels has no HIP kernel: ycx_ghost_dw "
+                                  f"takes the depthwise 5x5 / s1 / p2 conv")
+    if x.role in ('input', 'reorg'):  # the parser's rule (nets/yolo.py), for a module lowered on its own
+        raise NotImplementedError("ycx: GhostConv on the model input")
+    y = conv_module(g, m.cv1, x)
+    w, b = fold_bn(c.weight, m.cv2.bn)
+    return g.ghost(y, w, b, act_of(m.cv2.act), residual=residual)
+
+
+def conv_or_ghost(g: Graph, m, x: Val):
+    return ghostconv_module(g, m, x) if isinstance(m, GhostConv) else conv_module(g, m, x)
+
+
+def ghost_module(g: Graph, m: Ghost, x: Val):
+    """Ghost (nets/common.py:233-245): conv(x) + shortcut(x). The add runs over the second GhostConv's
+    concat, so it is that ghost node's residual: x itself for s = 1, the shortcut's 1x1 output for s = 2."""
+    first, dw, last = m.conv[0], m.conv[1], m.conv[2]
+    if isinstance(m.shortcut, nn.Identity):
+        c2 = 2 * last.cv2.conv.out_channels
+        if x.c != c2:
+            raise ValueError(f"ycx: Ghost with stride 1 needs c1 == c2, got {x.c} -> {c2} (the reference's add "
+                             f"fails there)")
+        r = x
+    else:
+        r = lower_module(g, m.shortcut, x)
+    y = ghostconv_module(g, first, x)
+    if not isinstance(dw, nn.Identity):
+        y = conv_module(g, dw, y)
+    return ghostconv_module(g, last, y, residual=r)
 
 
 def fold_robustconv(m: RobustConv):
@@ -280,6 +340,9 @@ def check_plan_precision(plan, precision):
     """What a plan cannot run in a given precision, raised before anything is allocated."""
     if precision == 'fp8' and any(nd.kind == 'deconv' for nd in plan.graph.nodes):
         raise NotImplementedError("ycx: transposed conv has no fp8 path (ycx_deconv2d takes bf16, fp16 and f32); "
+                                  "run this model in 'fp16', 'bf16' or 'f32'")
+    if precision == 'fp8' and any(nd.kind == 'ghost' for nd in plan.graph.nodes):
+        raise NotImplementedError("ycx: ghost conv has no fp8 path (ycx_ghost_dw takes bf16, fp16 and f32); "
                                   "run this model in 'fp16', 'bf16' or 'f32'")
     if precision == 'fp8' and any(nd.kind == 'gconv' for nd in plan.graph.nodes):
         raise NotImplementedError("ycx: grouped conv has no fp8 path (ycx_conv2d_grouped takes bf16, fp16 and f32); "
@@ -363,11 +426,16 @@ def lower_module(g: Graph, m, x):
         return deconv_module(g, m.conv_deconv, conv_module(g, m.conv_strided, x), w, b)
     if isinstance(m, nn.ConvTranspose2d):
         return deconv_module(g, m, x)
-    if isinstance(m, SPPCSPC):
-        x1 = conv_module(g, m.cv4, conv_module(g, m.cv3, conv_module(g, m.cv1, x)))
-        y1 = conv_module(g, m.cv6, conv_module(g, m.cv5, g.concat([x1] + pyramid(g, x1, list(m.m)))))
-        y2 = conv_module(g, m.cv2, x)
-        return conv_module(g, m.cv7, g.concat([y1, y2]))
+    if isinstance(m, GhostConv):
+        return ghostconv_module(g, m, x)
+    if isinstance(m, Ghost):
+        return ghost_module(g, m, x)
+    if isinstance(m, SPPCSPC):  # GhostSPPCSPC too: its cv1 .. cv7 are GhostConvs (nets/common.py:269-280)
+        cv = conv_or_ghost
+        x1 = cv(g, m.cv4, cv(g, m.cv3, cv(g, m.cv1, x)))
+        y1 = cv(g, m.cv6, cv(g, m.cv5, g.concat([x1] + pyramid(g, x1, list(m.m)))))
+        y2 = cv(g, m.cv2, x)
+        return cv(g, m.cv7, g.concat([y1, y2]))
     if isinstance(m, SPPF):
         x1 = conv_module(g, m.cv1, x)
         y1 = pool_module(g, m.m, x1)
@@ -377,7 +445,7 @@ def lower_module(g: Graph, m, x):
     if isinstance(m, SPP):
         x1 = conv_module(g, m.cv1, x)
         return conv_module(g, m.cv2, g.concat([x1] + pyramid(g, x1, list(m.m))))
-    # the CSP blocks: also their Res*CSP* / ResX*CSP* subclasses, whose m is a Sequential of Res
+    # the CSP blocks: also their Res*CSP* / ResX*CSP* / GhostCSP* subclasses, whose m is a Sequential of Res / Ghost
     if isinstance(m, BottleneckCSPA):
         y1 = lower_module(g, m.m, conv_module(g, m.cv1, x))
         return conv_module(g, m.cv3, g.concat([y1, conv_module(g, m.cv2, x)]))
@@ -456,11 +524,12 @@ class Plan:
     @property
     def conv_flops(self):
         """Algorithmic FLOPs: sum of 2*N*Ho*Wo*Cout*Cin*k*k over the folded convs (a grouped conv:
-        Cin = cin_g, the second dim of its weights), plus 2*N*H*W*Cin*s*s*Cout over the transposed convs
-        (each input pixel feeds an s x s block; weights [cin][cout][s][s])."""
+        Cin = cin_g, the second dim of its weights; a ghost node: its depthwise 5x5, 2*N*H*W*c*25), plus
+        2*N*H*W*Cin*s*s*Cout over the transposed convs (each input pixel feeds an s x s block; weights
+        [cin][cout][s][s])."""
         nodes = self.graph.nodes
         return sum(2 * nd.inputs[0].n * nd.p['ho'] * nd.p['wo'] * int(nd.p['w'].shape[0]) * int(nd.p['w'].shape[1])
-                   * nd.p['k'] ** 2 for nd in nodes if nd.kind in ('conv', 'stem', 'stem_reorg', 'gconv')) + \
+                   * nd.p['k'] ** 2 for nd in nodes if nd.kind in ('conv', 'stem', 'stem_reorg', 'gconv', 'ghost')) + \
             sum(2 * nd.inputs[0].n * nd.inputs[0].h * nd.inputs[0].w * int(nd.p['w'].shape[0]) * nd.p['s'] ** 2
                 * int(nd.p['w'].shape[1]) for nd in nodes if nd.kind == 'deconv')
 
@@ -522,12 +591,24 @@ class Plan:
             copies, off = [], 0
             for v in node.inputs:
                 if v.buf is None and v.role == 'act' and v.producer is not None and \
-                        v.producer.kind in ('conv', 'stem', 'stem_reorg', 'gconv', 'deconv', 'pool', 'up'):
+                        v.producer.kind in ('conv', 'stem', 'stem_reorg', 'gconv', 'deconv', 'ghost', 'pool', 'up'):
                     v.buf, v.coff = out.buf, off
                 else:
                     copies.append((v, off))
                 off += v.c
             node.p['copies'] = copies
+        # A residual-free ghost node runs in place: its hidden map y, when only it reads y, is stored by
+        # y's producer straight into the first half of the ghost's output, so no byte is copied. With a
+        # residual the first half is y + r, and y keeps a buffer of its own.
+        for node in g.nodes:
+            y, out = node.inputs[0] if node.kind == 'ghost' else None, node.out
+            if y is None or node.p['residual'] is not None or out.role != 'act':
+                continue
+            if y.buf is None and y.role == 'act' and len(y.consumers) == 1 and y.producer is not None and \
+                    y.producer.kind in ('conv', 'gconv') and y.producer.p['layout'] == L.OUT_NHWC:
+                if out.buf is None:
+                    out.buf = Buf(out.n, out.h, out.w, out.c)
+                y.buf, y.coff = out.buf, out.coff
         for node in g.nodes:
             v = node.out
             if v.buf is None and v.role == 'act':
@@ -706,7 +787,7 @@ class Engine:
         # size and the A/B switches, and a prepack file is reused at any batch size
         self.packed = {}
         self._conv_index = {id(nd): i for i, nd in enumerate(
-            nd for nd in self.graph.nodes if nd.kind in ('conv', 'stem', 'stem_reorg', 'gconv', 'deconv'))}
+            nd for nd in self.graph.nodes if nd.kind in ('conv', 'stem', 'stem_reorg', 'gconv', 'deconv', 'ghost'))}
         for b in self.schedule.activation_bufs:
             b.tensor = torch.empty((b.n, b.h, b.w, b.c), dtype=dt, device=dev)
             self.buffers.append(b.tensor)
@@ -718,6 +799,7 @@ class Engine:
                 'conv': lambda la: self._conv_op(*la.nodes),
                 'gconv': lambda la: self._gconv_op(*la.nodes),
                 'deconv': lambda la: self._deconv_op(*la.nodes),
+                'ghost': lambda la: self._ghost_op(*la.nodes),
                 'pool': lambda la: self._pool_op(la.nodes[0], levels=la.levels),
                 'copy': lambda la: self._copy_op(la.src, la.dst, la.off, la.scale, nchw=la.nchw)}
         ops = [emit[la.kind](la) for la in self.schedule.launches]
@@ -904,6 +986,54 @@ class Engine:
         self.op_info.append(dict(kind='gconv', name=f"gconv_g{cin_g}_k{k}s{p['s']}", flops=flops,
                                  shape=(x.n, x.h, x.w, x.c, cout, k, p['s']), parts=1, bytes=nbytes,
                                  out_bytes=nbytes - self._conv_bytes(d, wt, residual=r is not None, out_bytes=False)))
+        return op
+
+    def _ghost_op(self, node):
+        """One OP_GHOST (ycx_ghost_dw): fp32 weights [5][5][c][1] (the grouped kernel's packing) and fp32 bias
+        [c], unscaled; the descriptor has cin = c, cout = 2c. When the plan placed y in the first half of the
+        output the input and output pointers and slices coincide and the op runs in place."""
+        p, y, out, r = node.p, node.inputs[0], node.out, node.p['residual']
+        w64, b64 = p['w'], p['b']
+        c = int(w64.shape[0])
+        wshape, bshape = (5, 5, c, 1), (c,)
+        i = 2 * self._conv_index[id(node)]
+        if self.prepacked is not None:
+            wt, bt = self.prepacked.get(f"p{i}"), self.prepacked.get(f"p{i + 1}")
+            if wt is None or bt is None or tuple(wt.shape) != wshape or wt.dtype != torch.float32 or \
+                    tuple(bt.shape) != bshape or bt.dtype != torch.float32:
+                raise ValueError(f"ycx: prepacked weights do not match this plan at tensor p{i}")
+        else:
+            wt = w64.permute(2, 3, 0, 1).contiguous().to(torch.float32)
+            bt = b64.to(torch.float32)
+        wt, bt = wt.to(self.device), bt.to(self.device)
+        self.params += [wt, bt]
+        self.packed[f"p{i}"], self.packed[f"p{i + 1}"] = wt, bt
+        d = L.ConvDesc()
+        d.n, d.h, d.w, d.cin, d.in_c_off, d.in_c_stride = y.n, y.h, y.w, c, y.coff, y.buf.c
+        d.ho, d.wo, d.cout, d.cout_pad, d.out_c_off, d.out_c_stride = y.h, y.w, 2 * c, 2 * c, out.coff, out.buf.c
+        d.kh = d.kw = 5
+        d.stride, d.pad, d.act, d.leaky_slope = 1, 2, p['act'], p['slope']
+        d.dtype, d.out_layout, d.groups = self.dt, L.OUT_NHWC, c
+        if r is not None:
+            d.res_c_off, d.res_c_stride = r.coff, r.buf.c
+        d.out_scale = d.res_scale = 1.0
+        flops = 2 * y.n * y.h * y.w * c * 25
+        self.conv_flops += flops
+        op = L.Op()
+        op.kind = L.OP_GHOST
+        op.d.conv = d
+        op.in_ = y.buf.tensor.data_ptr()
+        op.weight, op.bias = wt.data_ptr(), bt.data_ptr()
+        op.out = out.buf.tensor.data_ptr()
+        op.residual = r.buf.tensor.data_ptr() if r is not None else None
+        inplace = y.buf is out.buf and y.coff == out.coff
+        isz = self.dtype.itemsize
+        px = y.n * y.h * y.w
+        out_bytes = px * c * isz * (1 if inplace else 2)  # in place: only the second half is stored
+        nbytes = px * c * isz + wt.numel() * 4 + (px * 2 * c * isz if r is not None else 0) + out_bytes
+        self.op_info.append(dict(kind='ghost', name='ghost_dw' + ('_inplace' if inplace else '') +
+                                 ('+res' if r is not None else ''), flops=flops, shape=(y.n, y.h, y.w, c, 2 * c, 5, 1),
+                                 parts=1, bytes=int(nbytes), out_bytes=int(out_bytes), inplace=inplace))
         return op
 
     def _deconv_op(self, node):
@@ -1165,10 +1295,10 @@ class Engine:
             if v:
                 setattr(o, field, v + i0 * per_image)
 
-        if o.kind in (L.OP_CONV, L.OP_STEM, L.OP_STEM2, L.OP_STEM_REORG, L.OP_GCONV, L.OP_DECONV):
+        if o.kind in (L.OP_CONV, L.OP_STEM, L.OP_STEM2, L.OP_STEM_REORG, L.OP_GCONV, L.OP_DECONV, L.OP_GHOST):
             d = o.d.pair[1] if o.kind == L.OP_STEM2 else o.d.conv
             first = o.d.pair[0] if o.kind == L.OP_STEM2 else d
-            if o.kind in (L.OP_CONV, L.OP_GCONV, L.OP_DECONV):
+            if o.kind in (L.OP_CONV, L.OP_GCONV, L.OP_DECONV, L.OP_GHOST):
                 shift('in_', (4 if d.in_pool else 1) * d.h * d.w * d.in_c_stride * es)
             else:  # fp32 NCHW image
                 shift('in_', first.cin * first.h * first.w * 4)
@@ -1198,7 +1328,7 @@ class Engine:
 
     @staticmethod
     def _op_out_h(op):
-        if op.kind in (L.OP_CONV, L.OP_STEM, L.OP_HEAD, L.OP_STEM_REORG, L.OP_GCONV, L.OP_DECONV):
+        if op.kind in (L.OP_CONV, L.OP_STEM, L.OP_HEAD, L.OP_STEM_REORG, L.OP_GCONV, L.OP_DECONV, L.OP_GHOST):
             return op.d.conv.ho
         if op.kind == L.OP_STEM2:
             return op.d.pair[1].ho

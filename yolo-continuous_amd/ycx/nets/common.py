@@ -72,6 +72,33 @@ class RobustConv2(_Holder):
         self.gamma = nn.Parameter(layer_scale_init_value * torch.ones(c2)) if layer_scale_init_value > 0 else None
 
 
+class GhostConv(_Holder):
+    """cat[y, cv2(y)] with y = cv1(x): a Conv to half the channels and a depthwise 5x5 / s1 Conv on its
+    output (nets/common.py:142-152). The engine runs cv2, the concat and Ghost's shortcut as one
+    ycx_ghost_dw launch."""
+
+    def __init__(self, c1, c2, k=1, s=1, g=1, act=True):
+        super().__init__()
+        c_ = c2 // 2
+        self.cv1 = Conv(c1, c_, k, s, None, g, act)
+        self.cv2 = Conv(c_, c_, 5, 1, None, c_, act)
+
+
+class Ghost(_Holder):
+    """conv(x) + shortcut(x): GhostConv, a depthwise k x k / s2 Conv when s == 2, GhostConv without
+    activation; the shortcut is the identity, or for s == 2 a depthwise Conv and a 1x1 Conv, both
+    without activation (nets/common.py:233-245)."""
+
+    def __init__(self, c1, c2, k=3, s=1):
+        super().__init__()
+        c_ = c2 // 2
+        self.conv = nn.Sequential(GhostConv(c1, c_, 1, 1),
+                                  dw_conv(c_, c_, k, s, act=False) if s == 2 else nn.Identity(),
+                                  GhostConv(c_, c2, 1, 1, act=False))
+        self.shortcut = nn.Sequential(dw_conv(c1, c1, k, s, act=False),
+                                      Conv(c1, c2, 1, 1, act=False)) if s == 2 else nn.Identity()
+
+
 class MP(_Holder):
     """MaxPool2d(k, k) (nets/common.py:25-31)."""
 
@@ -171,6 +198,22 @@ class SPPCSPC(_Holder):
         self.cv7 = Conv(2 * c_, c2, 1, 1)
 
 
+class GhostSPPCSPC(SPPCSPC):
+    """SPPCSPC with every Conv a GhostConv (nets/common.py:269-280). Like the reference it builds the
+    parent's plain convs first and then replaces them."""
+
+    def __init__(self, c1, c2, n=1, shortcut=False, g=1, e=0.5, k=(5, 9, 13)):
+        super().__init__(c1, c2, n, shortcut, g, e, k)
+        c_ = int(2 * c2 * e)
+        self.cv1 = GhostConv(c1, c_, 1, 1)
+        self.cv2 = GhostConv(c1, c_, 1, 1)
+        self.cv3 = GhostConv(c_, c_, 3, 1)
+        self.cv4 = GhostConv(c_, c_, 1, 1)
+        self.cv5 = GhostConv(4 * c_, c_, 1, 1)
+        self.cv6 = GhostConv(c_, c_, 3, 1)
+        self.cv7 = GhostConv(2 * c_, c2, 1, 1)
+
+
 class BottleneckCSPA(_Holder):
     """cv3(cat[m(cv1 x), cv2 x]) (nets/common.py:294-307)."""
 
@@ -260,6 +303,33 @@ class ResXCSPC(ResCSPC):
         super().__init__(c1, c2, n, shortcut, g, e)
         c_ = int(c2 * e)
         self.m = nn.Sequential(*[Res(c_, c_, shortcut, g, e=1.0) for _ in range(n)])
+
+
+class GhostCSPA(BottleneckCSPA):
+    """BottleneckCSPA over Ghost blocks (nets/common.py:392-397)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*[Ghost(c_, c_) for _ in range(n)])
+
+
+class GhostCSPB(BottleneckCSPB):
+    """BottleneckCSPB over Ghost blocks (nets/common.py:400-405)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2)
+        self.m = nn.Sequential(*[Ghost(c_, c_) for _ in range(n)])
+
+
+class GhostCSPC(BottleneckCSPC):
+    """BottleneckCSPC over Ghost blocks (nets/common.py:408-413)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*[Ghost(c_, c_) for _ in range(n)])
 
 
 class ImplicitA(_Holder):

@@ -26,8 +26,9 @@ from torch import nn
 
 from ..utils.helper_io import cvt_cfg
 from .common import (SP, SPP, SPPCSPC, SPPF, MP, Bottleneck, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC,
-                     Concat, Conv, DownC, ImplicitA, ImplicitM, ReOrg, RepConv, Res, ResCSPA, ResCSPB, ResCSPC, ResX,
-                     ResXCSPA, ResXCSPB, ResXCSPC, RobustConv, RobustConv2, dw_conv)
+                     Concat, Conv, DownC, Ghost, GhostConv, GhostCSPA, GhostCSPB, GhostCSPC, GhostSPPCSPC, ImplicitA,
+                     ImplicitM, ReOrg, RepConv, Res, ResCSPA, ResCSPB, ResCSPC, ResX, ResXCSPA, ResXCSPB, ResXCSPC,
+                     RobustConv, RobustConv2, dw_conv)
 from .detect import Detect, IAuxDetect, IDetect
 
 
@@ -46,21 +47,26 @@ _MODULES = {
     'nn.ConvTranspose2d': nn.ConvTranspose2d,
     'ResCSPA': ResCSPA, 'ResCSPB': ResCSPB, 'ResCSPC': ResCSPC,
     'ResXCSPA': ResXCSPA, 'ResXCSPB': ResXCSPB, 'ResXCSPC': ResXCSPC,
+    'GhostConv': GhostConv, 'Ghost': Ghost, 'GhostCSPA': GhostCSPA, 'GhostCSPB': GhostCSPB, 'GhostCSPC': GhostCSPC,
+    'GhostSPPCSPC': GhostSPPCSPC,
 }
 # Reference modules constructible by its parse_model but used by neither shipped
 # YAML: named here so the error says "out of scope", not "unknown".
 _OUT_OF_SCOPE = {
-    'Chuncat', 'Shortcut', 'Foldcut', 'GhostConv', 'Stem',
-    'Ghost', 'GhostSPPCSPC', 'GhostStem', 'Focus', 'Contract', 'Expand', 'Classify',
+    'Chuncat', 'Shortcut', 'Foldcut', 'Stem',
+    'GhostStem', 'Focus', 'Contract', 'Expand', 'Classify',
     'TransformerLayer', 'TransformerBlock', 'IBin', 'RepBottleneck',
-} | {f'{p}{s}' for p in ('RepRes', 'RepResX', 'Ghost', 'RepBottleneck')
+} | {f'{p}{s}' for p in ('RepRes', 'RepResX', 'RepBottleneck')
      for s in ('CSPA', 'CSPB', 'CSPC')}
+# The Ghost family runs on ycx_ghost_dw, which reads an NHWC activation: none of them can take the
+# fp32 NCHW image (like "grouped conv on the model input"), so there they stay out of scope.
+_GHOST_LIKE = (GhostConv, Ghost, GhostCSPA, GhostCSPB, GhostCSPC, GhostSPPCSPC)
 
 _CONV_LIKE = (nn.Conv2d, Conv, RobustConv, RobustConv2, dw_conv, RepConv, DownC, SPP, SPPF, SPPCSPC, Bottleneck,
               BottleneckCSPA, BottleneckCSPB, BottleneckCSPC, Res, ResCSPA, ResCSPB, ResCSPC, ResX, ResXCSPA, ResXCSPB,
-              ResXCSPC)
+              ResXCSPC, GhostConv, Ghost, GhostCSPA, GhostCSPB, GhostCSPC, GhostSPPCSPC)
 _CSP_LIKE = (DownC, SPPCSPC, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC, ResCSPA, ResCSPB, ResCSPC, ResXCSPA,
-             ResXCSPB, ResXCSPC)
+             ResXCSPB, ResXCSPC, GhostCSPA, GhostCSPB, GhostCSPC, GhostSPPCSPC)
 _ACTS = {'LeakyReLU': nn.LeakyReLU, 'SiLU': nn.SiLU, 'Identity': nn.Identity}
 _CALL_RE = re.compile(r'^(?:nn\.)?(\w+)\((.*)\)$')
 
@@ -103,7 +109,10 @@ def parse_model(d, ch, anchors, num_classes):
     no = na * (nc + 5)
     layers, save, c2 = [], [], ch[-1]
     for i, (f, n, m, args) in enumerate(d['backbone'] + d['head']):
-        m = _resolve_module(m)
+        name, m = m, _resolve_module(m)
+        if m in _GHOST_LIKE and i + (f if isinstance(f, int) else 0) < 0:  # f resolves to the image
+            raise NotImplementedError(f"ycx: module '{name}' on the model input is out of scope for the HIP "
+                                      f"inference path (ycx_ghost_dw reads an NHWC activation, not the image)")
         args = [_resolve_arg(a, nc, anchors) for a in args]
         n = max(round(n * gd), 1) if n > 1 else n
         if m in _CONV_LIKE:

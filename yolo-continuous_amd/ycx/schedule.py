@@ -27,6 +27,7 @@ class Launch:
     conv       nodes (conv,) or (conv, pool), the pool folded into the conv (kinds conv, stem, stem_reorg)
     gconv      nodes (gconv,)
     deconv     nodes (deconv,)
+    ghost      nodes (ghost,)
     pool       nodes: the cascade's pools, ``levels`` of them
     copy       nodes (up | concat | tonchw,): ``src`` -> channels from ``off`` of ``dst``, upsampled
                by ``scale`` (1 or 2), ``nchw``: to the fp32 NCHW output
@@ -249,7 +250,7 @@ class Schedule:
                 add('conv_pair', nd, pairs[i], *trio, store_a=len(nd.out.consumers) > 1 and not trio)
             elif k in ('conv', 'stem', 'stem_reorg'):
                 add('conv', nd, *([pooled[i]] if i in pooled else []))
-            elif k in ('gconv', 'deconv'):
+            elif k in ('gconv', 'deconv', 'ghost'):
                 add(k, nd)
             elif k == 'pool':
                 chain = cascades.get(i, [nd])
