@@ -17,9 +17,10 @@ Lowering (once per input shape / device / precision):
 3. Bind the schedule to memory: ``schedule.Schedule`` decides, without a device, which launches
    run the graph (stem pair, conv pair and trio, pooled 1x1, pool cascade) and which buffers
    they need. Allocate one NHWC device buffer per value (no reuse: a yolov7 bs=32 640x640 plan
-   is ~10 GB of bf16 activations, small next to 288 GB HBM), pack weights ([cout_pad][kh][kw][cin],
-   bf16 or fp32) and emit one op per launch into the ctypes array consumed by the native loop
-   ``ycx_run_ops`` (or a HIP graph).
+   is ~10 GB of bf16 activations, small next to 288 GB HBM), move the packed weights and descriptors
+   that ``ycx.pack`` decides, also without a device, onto it ([cout_pad][kh][kw][cin], bf16 or fp32)
+   and emit one op per launch into the ctypes array consumed by the native loop ``ycx_run_ops`` (or
+   a HIP graph).
 """
 from __future__ import annotations
 
@@ -32,10 +33,12 @@ import torch
 from torch import nn
 
 from . import _lib as L
+from . import pack
 from .nets.common import (SP, SPP, SPPCSPC, SPPF, MP, Bottleneck, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC,
                           Concat, Conv, DownC, Ghost, GhostConv, ReOrg, RepConv, Res, RobustConv, RobustConv2)
 from .nets.detect import Detect, IAuxDetect, IDetect
-from .schedule import Schedule, cascade_fits, cout_pad  # noqa: F401  (cascade_fits: re-exported)
+from .pack import pack_deconv_weights, pack_fp8_weights  # noqa: F401  (re-exported)
+from .schedule import Schedule, cascade_fits, cout_pad  # noqa: F401  (re-exported)
 
 
 class Buf:
@@ -523,15 +526,8 @@ class Plan:
 
     @property
     def conv_flops(self):
-        """Algorithmic FLOPs: sum of 2*N*Ho*Wo*Cout*Cin*k*k over the folded convs (a grouped conv:
-        Cin = cin_g, the second dim of its weights; a ghost node: its depthwise 5x5, 2*N*H*W*c*25), plus
-        2*N*H*W*Cin*s*s*Cout over the transposed convs (each input pixel feeds an s x s block; weights
-        [cin][cout][s][s])."""
-        nodes = self.graph.nodes
-        return sum(2 * nd.inputs[0].n * nd.p['ho'] * nd.p['wo'] * int(nd.p['w'].shape[0]) * int(nd.p['w'].shape[1])
-                   * nd.p['k'] ** 2 for nd in nodes if nd.kind in ('conv', 'stem', 'stem_reorg', 'gconv', 'ghost')) + \
-            sum(2 * nd.inputs[0].n * nd.inputs[0].h * nd.inputs[0].w * int(nd.p['w'].shape[0]) * nd.p['s'] ** 2
-                * int(nd.p['w'].shape[1]) for nd in nodes if nd.kind == 'deconv')
+        """Algorithmic FLOPs of the folded convs of every kind (``pack.flops``)."""
+        return sum(pack.flops(nd) for nd in self.graph.nodes if nd.kind in pack.CONV_KINDS)
 
     def counts(self):
         """Node kinds after the passes; 'conv' counts the original convs (a merged
@@ -661,30 +657,6 @@ class Plan:
                     break
 
 
-def pack_fp8_weights(wp):
-    """float64 [cout_pad][cin][k][k] -> (e4m3 [cout_pad][ceil(k*k*cin / 128) * 128] as
-    torch.float8_e4m3fn, float64 s_w[cout_pad]): per output channel the
-    power-of-two scale that maps its max |w| into [224, 448], rows in
-    [kh][kw][cin] order, zero-padded to whole 128-byte K steps (ycx.h)."""
-    cpad = wp.shape[0]
-    amax = wp.abs().amax(dim=(1, 2, 3))
-    sw = torch.where(amax > 0, torch.exp2(torch.floor(torch.log2(448.0 / amax.clamp_min(1e-300)))),
-                     torch.ones_like(amax))
-    rows = (wp * sw.reshape(-1, 1, 1, 1)).permute(0, 2, 3, 1).reshape(cpad, -1)
-    kt = rows.shape[1]
-    ktp = -(-kt // 128) * 128
-    out = torch.zeros((cpad, ktp), dtype=torch.float32)
-    out[:, :kt] = rows.to(torch.float32)
-    return out.clamp(-448.0, 448.0).to(torch.float8_e4m3fn), sw
-
-
-def pack_deconv_weights(w64, dtype):
-    """float64 [cin][cout][s][s] (torch's ConvTranspose2d layout) -> [s*s][cout][cin] in ``dtype``: the rows
-    of ycx_deconv2d's GEMM, tap-major (tap = dy * s + dx), K = cin contiguous (include/ycx.h)."""
-    cin, cout, s = int(w64.shape[0]), int(w64.shape[1]), int(w64.shape[2])
-    return w64.permute(2, 3, 1, 0).reshape(s * s, cout, cin).contiguous().to(dtype)
-
-
 class Engine:
     """A compiled plan bound to device memory for one (input shape, device, precision)."""
 
@@ -747,7 +719,10 @@ class Engine:
             self.scales[id(b)] = 2.0 ** math.floor(math.log2(224.0 / m)) if m > 0 and math.isfinite(m) else 1.0
 
     def _scale(self, v):
-        return self.scales.get(id(v.buf), 1.0) if v.buf is not None else 1.0
+        return pack.scale_of(self.scales, v)
+
+    def _conv_bytes(self, d, wt, **kw):
+        return pack.conv_bytes(d, wt, self.dtype.itemsize, **kw)
 
     def _pair_op(self, a, b, c=None, pool=None, store_a=False):
         """One OP_CONV_PAIR for the chain a -> b (``schedule.conv_pairs``); with c (``schedule.pair_pools``)
@@ -782,12 +757,8 @@ class Engine:
     def _build(self):
         dev, dt = self.device, self.dtype
         self.buffers, self.params = [], []
-        # packed tensors are named by the conv's position among the graph's conv / stem nodes,
-        # not by packing order: which convs fuse (stem pair, 1x1 pair) varies with the batch
-        # size and the A/B switches, and a prepack file is reused at any batch size
-        self.packed = {}
-        self._conv_index = {id(nd): i for i, nd in enumerate(
-            nd for nd in self.graph.nodes if nd.kind in ('conv', 'stem', 'stem_reorg', 'gconv', 'deconv', 'ghost'))}
+        self.packed = {}  # {'p<i>': packed tensor}, named by graph position (``pack.conv_index``)
+        self._conv_index = pack.conv_index(self.graph.nodes)
         for b in self.schedule.activation_bufs:
             b.tensor = torch.empty((b.n, b.h, b.w, b.c), dtype=dt, device=dev)
             self.buffers.append(b.tensor)
@@ -797,9 +768,9 @@ class Engine:
         emit = {'stem2': lambda la: self._stem2_op(*la.nodes),
                 'conv_pair': lambda la: self._pair_op(*la.nodes, store_a=la.store_a),
                 'conv': lambda la: self._conv_op(*la.nodes),
-                'gconv': lambda la: self._gconv_op(*la.nodes),
-                'deconv': lambda la: self._deconv_op(*la.nodes),
-                'ghost': lambda la: self._ghost_op(*la.nodes),
+                'gconv': lambda la: self._plain_op(la.nodes[0], L.OP_GCONV, 'gconv_g{g}_k{k}s{s}'),
+                'deconv': lambda la: self._plain_op(la.nodes[0], L.OP_DECONV, 'deconv_s{s}'),
+                'ghost': lambda la: self._plain_op(la.nodes[0], L.OP_GHOST, 'ghost_dw'),
                 'pool': lambda la: self._pool_op(la.nodes[0], levels=la.levels),
                 'copy': lambda la: self._copy_op(la.src, la.dst, la.off, la.scale, nchw=la.nchw)}
         ops = [emit[la.kind](la) for la in self.schedule.launches]
@@ -826,85 +797,28 @@ class Engine:
         return v.buf.tensor.data_ptr()
 
     def _conv_parts(self, node, bf16_weights=False, pool=None):
-        """Packed weights/bias (kept alive in self.params) and the descriptor of a conv/stem node.
+        """Packed weights/bias (prepacked or ``pack.pack``; on the device, kept alive in self.params and named
+        in self.packed), the descriptor (``pack.desc``), the FLOPs and the op_info shape of a conv-kind node.
         bf16_weights: 16-bit packing whatever the plan dtype (the fp8 stem2 pair computes in bf16;
         an fp16 plan's pair in fp16).
         pool: the k2 s2 pool node feeding this 1x1 conv, fused into it (``schedule.pool_convs``)."""
-        p, x, out = node.p, node.inputs[0], node.out
-        w64, b64 = p['w'], p['b']
-        cout, cin, k = int(w64.shape[0]), int(w64.shape[1]), p['k']
-        stem = node.kind in ('stem', 'stem_reorg')
-        cpad = cout_pad(self.precision, cout, stem or bf16_weights)
-        f8 = self.dt == L.DT_FP8
-        if stem:  # [kh][kw][cin][cout_pad] fp32
-            wshape, wdt = (k, k, cin, cpad), torch.float32
-        elif bf16_weights:
-            wshape, wdt = (cpad, k, k, cin), (torch.float16 if self.dt == L.DT_F16 else torch.bfloat16)
-        elif f8:  # e4m3 rows of w * s_w[co], [cout_pad][kh*kw*cin padded to 128 B]
-            wshape, wdt = (cpad, -(-k * k * cin // 128) * 128), torch.float8_e4m3fn
-        else:     # [cout_pad][kh][kw][cin] in the activation dtype
-            wshape, wdt = (cpad, k, k, cin), self.dtype
-        bshape = (2 * cpad,) if (f8 and not stem and not bf16_weights) else (cpad,)
-        # SiLU epilogues of the 16-bit / fp8 plans run on c' = -log2(e) c (YCX_ACT_SILU_PS): the weights
-        # and bias are scaled here in float64 before their one rounding (fp8: the fp32 bias and dq rows,
-        # so the e4m3 weights are unchanged); the fp32 parity plan keeps torch's silu(c) = c / (1 + e^-c)
-        silu_ps = p['act'] == L.ACT_SILU and self.dt != L.DT_F32 and not _NO_SILU_PS
+        # SiLU epilogues of the 16-bit / fp8 plans run pre-scaled (YCX_ACT_SILU_PS, ``pack``): dense convs only;
+        # the fp32 parity plan keeps torch's silu(c) = c / (1 + e^-c)
+        silu_ps = (node.kind in pack.DENSE and node.p['act'] == L.ACT_SILU and self.dt != L.DT_F32
+                   and not _NO_SILU_PS)
         i = 2 * self._conv_index[id(node)]
         if self.prepacked is not None:
-            wt, bt = self.prepacked.get(f"p{i}"), self.prepacked.get(f"p{i + 1}")
-            if wt is None or bt is None or tuple(wt.shape) != wshape or wt.dtype != wdt or \
-                    tuple(bt.shape) != bshape or bt.dtype != torch.float32:
-                raise ValueError(f"ycx: prepacked weights do not match this plan at tensor p{i}")
+            wt, bt = pack.take_prepacked(self.prepacked, i, pack.spec(node, self.precision, bf16_weights))
         else:
-            wp = torch.zeros((cpad, cin, k, k), dtype=torch.float64)
-            wp[:cout] = w64
-            bp = torch.zeros(cpad, dtype=torch.float64)
-            bp[:cout] = b64
-            ks = L.SILU_PS_K if silu_ps else 1.0
-            if not (f8 and not stem and not bf16_weights):
-                wp, bp = wp * ks, bp * ks
-            if stem:
-                wt = wp.permute(2, 3, 1, 0).contiguous().to(torch.float32)
-            elif bf16_weights:
-                wt = wp.permute(0, 2, 3, 1).contiguous().to(wdt)
-            elif f8:
-                wt, sw = pack_fp8_weights(wp)
-                bp = torch.cat([bp * ks, ks / (sw * self._scale(x))])  # dq[co] = 1 / (s_w[co] s_x), both x ks
-            else:
-                wt = wp.permute(0, 2, 3, 1).contiguous().to(self.dtype)
-            bt = bp.to(torch.float32)
-        wt = wt.to(self.device)
-        bt = bt.to(self.device)
+            wt, bt = pack.pack(node, self.precision, bf16_weights=bf16_weights, silu_ps=silu_ps,
+                               in_scale=self._scale(node.inputs[0]))
+        wt, bt = wt.to(self.device), bt.to(self.device)
         self.params += [wt, bt]
         self.packed[f"p{i}"], self.packed[f"p{i + 1}"] = wt, bt
-        d = L.ConvDesc()
-        d.n, d.h, d.w, d.cin = x.n, x.h, x.w, cin
-        if x.role == 'input':
-            d.in_c_off, d.in_c_stride = 0, x.c
-        elif x.role == 'reorg':  # the image's own channel count; d.h, d.w, d.cin describe the reorganised map
-            d.in_c_off, d.in_c_stride = 0, x.c // 4
-        else:
-            d.in_c_off, d.in_c_stride = x.coff, x.buf.c
-        if pool is not None:  # read the pool's (2h, 2w) input map instead of its output
-            src = pool.inputs[0]
-            d.in_c_off, d.in_c_stride, d.in_pool = src.coff, src.buf.c, 1
-        d.ho, d.wo, d.cout, d.cout_pad = p['ho'], p['wo'], cout, cpad
-        d.kh = d.kw = k
-        d.stride, d.pad, d.act, d.leaky_slope = p['s'], p['p'], (L.ACT_SILU_PS if silu_ps else p['act']), p['slope']
-        d.dtype, d.out_layout = self.dt, p['layout']
-        if p['layout'] == L.OUT_NCHW_F32:
-            d.out_c_off, d.out_c_stride = 0, cout
-        else:
-            d.out_c_off, d.out_c_stride = out.coff, out.buf.c
-        r = p['residual']
-        if r is not None:
-            d.res_c_off, d.res_c_stride = r.coff, r.buf.c
-        d.tile = 0
-        d.out_scale = self._scale(out) if (f8 and p['layout'] != L.OUT_NCHW_F32) else 1.0
-        d.res_scale = 1.0 / self._scale(r) if (f8 and r is not None) else 1.0
-        flops = 2 * x.n * p['ho'] * p['wo'] * cout * cin * k * k
+        d = pack.desc(node, self.precision, bf16_weights=bf16_weights, silu_ps=silu_ps, scales=self.scales, pool=pool)
+        flops = pack.flops(node)
         self.conv_flops += flops
-        return d, wt, bt, flops, (x.n, x.h, x.w, cin, cout, k, p['s'])
+        return d, wt, bt, flops, (d.n, d.h, d.w, d.cin, d.cout, d.kh, d.stride)
 
     def _conv_op(self, node, pool=None):
         x, out, r = node.inputs[0], node.out, node.p['residual']
@@ -945,154 +859,30 @@ class Engine:
                                  bytes=nbytes, out_bytes=nbytes - self._conv_bytes(d, wt, out_bytes=False, **kw)))
         return op
 
-    def _gconv_op(self, node):
-        """One OP_GCONV (ycx_conv2d_grouped): fp32 weights [kh][kw][cout][cin_g] and fp32 bias [cout] in every
-        precision, unscaled -- a SiLU gconv runs the plain YCX_ACT_SILU epilogue, never the pre-scaled one."""
-        p, x, out, r = node.p, node.inputs[0], node.out, node.p['residual']
-        w64, b64 = p['w'], p['b']
-        cout, cin_g, k = int(w64.shape[0]), int(w64.shape[1]), p['k']
-        wshape, bshape = (k, k, cout, cin_g), (cout,)
-        i = 2 * self._conv_index[id(node)]
-        if self.prepacked is not None:
-            wt, bt = self.prepacked.get(f"p{i}"), self.prepacked.get(f"p{i + 1}")
-            if wt is None or bt is None or tuple(wt.shape) != wshape or wt.dtype != torch.float32 or \
-                    tuple(bt.shape) != bshape or bt.dtype != torch.float32:
-                raise ValueError(f"ycx: prepacked weights do not match this plan at tensor p{i}")
-        else:
-            wt = w64.permute(2, 3, 0, 1).contiguous().to(torch.float32)
-            bt = b64.to(torch.float32)
-        wt, bt = wt.to(self.device), bt.to(self.device)
-        self.params += [wt, bt]
-        self.packed[f"p{i}"], self.packed[f"p{i + 1}"] = wt, bt
-        d = L.ConvDesc()
-        d.n, d.h, d.w, d.cin, d.in_c_off, d.in_c_stride = x.n, x.h, x.w, x.c, x.coff, x.buf.c
-        d.ho, d.wo, d.cout, d.cout_pad, d.out_c_off, d.out_c_stride = p['ho'], p['wo'], cout, cout, out.coff, out.buf.c
-        d.kh = d.kw = k
-        d.stride, d.pad, d.act, d.leaky_slope = p['s'], p['p'], p['act'], p['slope']
-        d.dtype, d.out_layout, d.groups = self.dt, L.OUT_NHWC, p['groups']
-        if r is not None:
-            d.res_c_off, d.res_c_stride = r.coff, r.buf.c
-        d.out_scale = d.res_scale = 1.0
-        flops = 2 * x.n * p['ho'] * p['wo'] * cout * cin_g * k * k
-        self.conv_flops += flops
+    def _plain_op(self, node, kind, name):
+        """One OP_GCONV / OP_DECONV / OP_GHOST (ycx_conv2d_grouped, ycx_deconv2d, ycx_ghost_dw): no tile, no
+        split-K, plain YCX_ACT_* epilogues. When the plan placed a ghost's y in the first half of its output,
+        the input and output pointers and slices coincide and the op runs in place."""
+        x, out, r = node.inputs[0], node.out, node.p['residual']
+        d, wt, bt, flops, shape = self._conv_parts(node)
         op = L.Op()
-        op.kind = L.OP_GCONV
+        op.kind = kind
         op.d.conv = d
         op.in_ = x.buf.tensor.data_ptr()
         op.weight, op.bias = wt.data_ptr(), bt.data_ptr()
         op.out = out.buf.tensor.data_ptr()
         op.residual = r.buf.tensor.data_ptr() if r is not None else None
-        nbytes = self._conv_bytes(d, wt, residual=r is not None)
-        self.op_info.append(dict(kind='gconv', name=f"gconv_g{cin_g}_k{k}s{p['s']}", flops=flops,
-                                 shape=(x.n, x.h, x.w, x.c, cout, k, p['s']), parts=1, bytes=nbytes,
-                                 out_bytes=nbytes - self._conv_bytes(d, wt, residual=r is not None, out_bytes=False)))
+        inplace = kind == L.OP_GHOST and x.buf is out.buf and x.coff == out.coff
+        # in place: only the second half is stored
+        nbytes = self._conv_bytes(d, wt, residual=r is not None) - (
+            d.n * d.h * d.w * d.cin * self.dtype.itemsize if inplace else 0)
+        info = dict(kind=node.kind, name=name.format(g=d.cin // max(1, d.groups), k=d.kh, s=d.stride), flops=flops,
+                    shape=shape, parts=1, bytes=nbytes,
+                    out_bytes=nbytes - self._conv_bytes(d, wt, residual=r is not None, out_bytes=False))
+        if kind == L.OP_GHOST:
+            info.update(name=name + ('_inplace' if inplace else '') + ('+res' if r is not None else ''), inplace=inplace)
+        self.op_info.append(info)
         return op
-
-    def _ghost_op(self, node):
-        """One OP_GHOST (ycx_ghost_dw): fp32 weights [5][5][c][1] (the grouped kernel's packing) and fp32 bias
-        [c], unscaled; the descriptor has cin = c, cout = 2c. When the plan placed y in the first half of the
-        output the input and output pointers and slices coincide and the op runs in place."""
-        p, y, out, r = node.p, node.inputs[0], node.out, node.p['residual']
-        w64, b64 = p['w'], p['b']
-        c = int(w64.shape[0])
-        wshape, bshape = (5, 5, c, 1), (c,)
-        i = 2 * self._conv_index[id(node)]
-        if self.prepacked is not None:
-            wt, bt = self.prepacked.get(f"p{i}"), self.prepacked.get(f"p{i + 1}")
-            if wt is None or bt is None or tuple(wt.shape) != wshape or wt.dtype != torch.float32 or \
-                    tuple(bt.shape) != bshape or bt.dtype != torch.float32:
-                raise ValueError(f"ycx: prepacked weights do not match this plan at tensor p{i}")
-        else:
-            wt = w64.permute(2, 3, 0, 1).contiguous().to(torch.float32)
-            bt = b64.to(torch.float32)
-        wt, bt = wt.to(self.device), bt.to(self.device)
-        self.params += [wt, bt]
-        self.packed[f"p{i}"], self.packed[f"p{i + 1}"] = wt, bt
-        d = L.ConvDesc()
-        d.n, d.h, d.w, d.cin, d.in_c_off, d.in_c_stride = y.n, y.h, y.w, c, y.coff, y.buf.c
-        d.ho, d.wo, d.cout, d.cout_pad, d.out_c_off, d.out_c_stride = y.h, y.w, 2 * c, 2 * c, out.coff, out.buf.c
-        d.kh = d.kw = 5
-        d.stride, d.pad, d.act, d.leaky_slope = 1, 2, p['act'], p['slope']
-        d.dtype, d.out_layout, d.groups = self.dt, L.OUT_NHWC, c
-        if r is not None:
-            d.res_c_off, d.res_c_stride = r.coff, r.buf.c
-        d.out_scale = d.res_scale = 1.0
-        flops = 2 * y.n * y.h * y.w * c * 25
-        self.conv_flops += flops
-        op = L.Op()
-        op.kind = L.OP_GHOST
-        op.d.conv = d
-        op.in_ = y.buf.tensor.data_ptr()
-        op.weight, op.bias = wt.data_ptr(), bt.data_ptr()
-        op.out = out.buf.tensor.data_ptr()
-        op.residual = r.buf.tensor.data_ptr() if r is not None else None
-        inplace = y.buf is out.buf and y.coff == out.coff
-        isz = self.dtype.itemsize
-        px = y.n * y.h * y.w
-        out_bytes = px * c * isz * (1 if inplace else 2)  # in place: only the second half is stored
-        nbytes = px * c * isz + wt.numel() * 4 + (px * 2 * c * isz if r is not None else 0) + out_bytes
-        self.op_info.append(dict(kind='ghost', name='ghost_dw' + ('_inplace' if inplace else '') +
-                                 ('+res' if r is not None else ''), flops=flops, shape=(y.n, y.h, y.w, c, 2 * c, 5, 1),
-                                 parts=1, bytes=int(nbytes), out_bytes=int(out_bytes), inplace=inplace))
-        return op
-
-    def _deconv_op(self, node):
-        """One OP_DECONV (ycx_deconv2d): weights [s*s][cout][cin] in the activation dtype, fp32 bias [cout],
-        unscaled (plain YCX_ACT_* epilogues)."""
-        p, x, out = node.p, node.inputs[0], node.out
-        cin, cout, s = int(p['w'].shape[0]), int(p['w'].shape[1]), p['s']
-        wshape, bshape = (s * s, cout, cin), (cout,)
-        i = 2 * self._conv_index[id(node)]
-        if self.prepacked is not None:
-            wt, bt = self.prepacked.get(f"p{i}"), self.prepacked.get(f"p{i + 1}")
-            if wt is None or bt is None or tuple(wt.shape) != wshape or wt.dtype != self.dtype or \
-                    tuple(bt.shape) != bshape or bt.dtype != torch.float32:
-                raise ValueError(f"ycx: prepacked weights do not match this plan at tensor p{i}")
-        else:
-            wt, bt = pack_deconv_weights(p['w'], self.dtype), p['b'].to(torch.float32)
-        wt, bt = wt.to(self.device), bt.to(self.device)
-        self.params += [wt, bt]
-        self.packed[f"p{i}"], self.packed[f"p{i + 1}"] = wt, bt
-        d = L.ConvDesc()
-        d.n, d.h, d.w, d.cin, d.in_c_off, d.in_c_stride = x.n, x.h, x.w, cin, x.coff, x.buf.c
-        d.ho, d.wo, d.cout, d.cout_pad, d.out_c_off, d.out_c_stride = p['ho'], p['wo'], cout, cout, out.coff, out.buf.c
-        d.kh = d.kw = d.stride = s
-        d.pad, d.act, d.leaky_slope = 0, p['act'], p['slope']
-        d.dtype, d.out_layout = self.dt, L.OUT_NHWC
-        d.out_scale = d.res_scale = 1.0
-        flops = 2 * x.n * x.h * x.w * cin * s * s * cout
-        self.conv_flops += flops
-        op = L.Op()
-        op.kind = L.OP_DECONV
-        op.d.conv = d
-        op.in_ = x.buf.tensor.data_ptr()
-        op.weight, op.bias = wt.data_ptr(), bt.data_ptr()
-        op.out = out.buf.tensor.data_ptr()
-        nbytes = self._conv_bytes(d, wt)
-        self.op_info.append(dict(kind='deconv', name=f"deconv_s{s}", flops=flops, shape=(x.n, x.h, x.w, cin, cout, s, s),
-                                 parts=1, bytes=nbytes, out_bytes=nbytes - self._conv_bytes(d, wt, out_bytes=False)))
-        return op
-
-    def _conv_bytes(self, d, wt, stem=False, pooled=False, residual=False, out_bytes=True):
-        """Algorithmic HBM bytes of one conv launch: its input map read once (the
-        fp32 NCHW image for a stem -- a stem_reorg's 4C x h x w is the same C x 2h x 2w image --; the 2x2-larger source map when an MP pool is
-        fused in), the packed weights once, the residual once, the output written
-        once (4x for the fused x2 upsample; fp32 for NCHW heads). The per-op
-        roofline in bench.py prices each op against max(FLOP / MFMA peak, these
-        bytes / HBM peak)."""
-        isz = self.dtype.itemsize
-        px_in = d.n * d.h * d.w * (4 if pooled else 1)
-        b = px_in * d.cin * (4 if stem else isz)
-        b += wt.numel() * wt.element_size()
-        px_out = d.n * d.ho * d.wo
-        if residual:
-            b += px_out * d.cout * isz
-        if out_bytes:
-            if d.out_layout == L.OUT_NCHW_F32:
-                b += px_out * d.cout * 4
-            else:
-                b += px_out * d.cout * isz * (4 if d.out_layout == L.OUT_NHWC_UP2 else 1)
-        return int(b)
 
     def _stem2_op(self, stem, conv):
         ds, ws, bs, fs, _ = self._conv_parts(stem)

@@ -4,7 +4,7 @@ A reference checkpoint is a 558-key ``state_dict`` (``train.py:116`` saves it,
 ``detect.py:175`` loads it). Lowering it for the HIP path folds BN, RepConv and
 ImplicitA/M in float64 (``nets/common.py:488-529``) and packs every conv as
 ``[cout_pad][kh][kw][cin]`` bf16 / fp32, or per-channel-scaled e4m3 rows plus the
-dequantisation vector for fp8 (``ycx/engine.py``). This module stores that
+dequantisation vector for fp8 (``ycx/pack.py`` states every layout). This module stores that
 result, with the fp8 calibration record it depends on, in one safetensors file
 so a serving process skips the host-side folding and calibration.
 
