@@ -27,6 +27,8 @@
  *   ycx_maxpool         MP / SP / SPPCSPC max-pools             nets/common.py:25-40, 257
  *   ycx_copy_channels   nn.Upsample(None, 2, 'nearest')         cfg/net/yolov7.yaml:71,85
  *                       Concat (only when a slice cannot alias)  nets/common.py:54-60
+ *   ycx_space_depth     Contract, Expand                         nets/common.py:787-812
+ *                       Focus's pixel-phase cat on an activation nets/common.py:767
  *   ycx_decode          decode_box (one head level)             detect.py:29-87
  *   ycx_filter_decoded  non_max_suppression lines 98-121        detect.py:98-121
  *   ycx_decode_filter   decode_box + the same filter, fused     detect.py:29-121
@@ -55,7 +57,9 @@ extern "C" {
  * an entry point and an op kind but no struct and no field: the library and its ctypes mirror
  * (ycx/_lib.py) are always built together in-tree and check each other's struct sizes
  * (ycx_struct_size, ids 0 to 11 unchanged) at load time; a zero-initialised descriptor
- * means what it meant before. */
+ * means what it meant before. ycx_space_depth / YCX_OP_DEPTH add ycx_depth_desc, a new member of
+ * ycx_op's union that is smaller than `pair`, so sizeof(ycx_op) and the ids 0 to 11 stay as they are;
+ * the new struct has no id (the ctypes mirror is checked through sizeof(ycx_op)). */
 #define YCX_ABI_VERSION 9
 
 typedef int32_t ycx_status;
@@ -169,6 +173,18 @@ typedef struct ycx_copy_desc {
   float dequant;            /* YCX_DT_FP8 with YCX_OUT_NCHW_F32: 1 / s_in (else unused) */
 } ycx_copy_desc;
 
+/* Space <-> depth move between two NHWC channel slices (ycx_space_depth, below). n, h, w, c describe
+ * the input slice, ho, wo the output map; the output slice is c * gain^2 (Contract, Focus) or
+ * c / gain^2 (Expand) channels wide. */
+enum { YCX_SD_CONTRACT = 0, YCX_SD_EXPAND = 1, YCX_SD_FOCUS = 2 };
+typedef struct ycx_depth_desc {
+  int32_t n, h, w, c, in_c_off, in_c_stride;
+  int32_t ho, wo, out_c_off, out_c_stride;
+  int32_t gain;             /* s, 2 .. 4 (YCX_SD_FOCUS: 2)                          */
+  int32_t mode;             /* YCX_SD_*                                             */
+  int32_t dtype;            /* YCX_DT_*: moved as bytes                             */
+} ycx_depth_desc;
+
 /* Decode of one head level (detect.py:29-87 semantics). head is fp32 NCHW
  * [n][na*no][h][w]; out is fp32 [n][rows_total][no], written at row_off.
  * anchors_scaled[2a], [2a+1] = anchor_w/stride_w, anchor_h/stride_h computed in
@@ -253,7 +269,8 @@ enum { YCX_OP_CONV = 1, YCX_OP_STEM = 2, YCX_OP_POOL = 3, YCX_OP_COPY = 4, YCX_O
        YCX_OP_STEM_REORG = 8 /* ycx_stem_conv_reorg: d.conv, in, weight, bias, out */,
        YCX_OP_GCONV = 9 /* ycx_conv2d_grouped: d.conv, in, weight (fp32), bias, out, residual */,
        YCX_OP_DECONV = 10 /* ycx_deconv2d: d.conv, in, weight, bias, out */,
-       YCX_OP_GHOST = 11 /* ycx_ghost_dw: d.conv, in, weight (fp32), bias, out, residual */ };
+       YCX_OP_GHOST = 11 /* ycx_ghost_dw: d.conv, in, weight (fp32), bias, out, residual */,
+       YCX_OP_DEPTH = 12 /* ycx_space_depth: d.depth, in, out */ };
 typedef struct ycx_op {
   int32_t kind;
   int32_t pad_;
@@ -261,6 +278,7 @@ typedef struct ycx_op {
     ycx_conv_desc conv;
     ycx_pool_desc pool;
     ycx_copy_desc copy;
+    ycx_depth_desc depth;   /* DEPTH                                                 */
     ycx_conv_desc pair[2];  /* STEM2: [0] the stem, [1] the stride-2 conv it feeds;
                                CONV_PAIR: [0] the first 1x1 conv, [1] the 1x1 conv reading it */
     struct {
@@ -443,6 +461,27 @@ ycx_status ycx_stem_conv_reorg(const ycx_conv_desc* d, const float* x, const flo
                                const float* bias, void* y, void* stream);
 ycx_status ycx_maxpool(const ycx_pool_desc* d, const void* x, void* y, void* stream);
 ycx_status ycx_copy_channels(const ycx_copy_desc* d, const void* x, void* y, void* stream);
+/* Space <-> depth on an NHWC activation: Contract and Expand (nets/common.py:787-812) and the pixel-phase
+ * concat inside Focus.forward (:767), a pure move between two channel slices (the in_c_* / out_c_*
+ * convention of ycx_copy_channels, so y may be a slice of a concat buffer). s = d->gain, C = d->c:
+ *   YCX_SD_CONTRACT  y [n][h/s][w/s][s*s*C]:        y[n, ho, wo, (a*s+b)*C + c] = x[n, ho*s+a, wo*s+b, c]
+ *   YCX_SD_EXPAND    y [n][h*s][w*s][C'], C' = C/(s*s): y[n, h*s+a, w*s+b, c'] = x[n, h, w, (a*s+b)*C' + c']
+ *   YCX_SD_FOCUS     y [n][h/2][w/2][4C], s == 2:   y[n, ho, wo, (2*b+a)*C + c] = x[n, 2*ho+a, 2*wo+b, c]
+ * Expand is the inverse of Contract. In Focus the row phase varies fastest: the C-channel blocks come in
+ * the order (a, b) = (0,0), (1,0), (0,1), (1,1), ReOrg's order (ycx_stem_conv_reorg).
+ * dtype bf16 / fp16 / f32 / fp8, moved as 2-, 2-, 4- and 1-byte elements: NaN payloads, -0.0 and every
+ * e4m3 code pass through unchanged; fp8 input and output share one scale. The contiguous channel run
+ * (C for Contract and Focus, C' for Expand) and every channel offset and stride are multiples of 8
+ * elements. Each lane moves one vector of up to 16 bytes; consecutive lanes store consecutive output
+ * vectors (the store side is fully coalesced, the load side reads whole runs); a grid-stride loop over a
+ * 64-bit flat index; no LDS.
+ * YCX_ERR_BAD_ARG before any device call: null pointers, n <= 0, h % s or w % s non-zero (Contract,
+ * Focus), C % (s*s) non-zero (Expand), ho / wo not what h, w and s imply, a slice past its stride,
+ * x == y unless the two slices have one pixel stride and disjoint channel ranges.
+ * YCX_ERR_UNSUPPORTED: a gain outside 2 .. 4, Focus with s != 2, a run, offset or stride that is no
+ * multiple of 8, an unknown dtype or mode. The descriptor is judged before the data pointers, as in
+ * ycx_conv2d_grouped. */
+ycx_status ycx_space_depth(const ycx_depth_desc* d, const void* x, void* y, void* stream);
 /* fp32 -> OCP e4m3fn bytes: y[i] = e4m3(clamp(x[i] * scale, +-448)), round to
  * nearest even: the exact cast of the YCX_DT_FP8 epilogues (calibration checks). */
 ycx_status ycx_quantize_fp8(const float* x, void* y, int64_t n, float scale, void* stream);

@@ -30,6 +30,8 @@ OP_CONV, OP_STEM, OP_POOL, OP_COPY, OP_STEM2, OP_HEAD, OP_CONV_PAIR, OP_STEM_REO
 OP_GCONV = 9
 OP_DECONV = 10
 OP_GHOST = 11
+OP_DEPTH = 12
+SD_CONTRACT, SD_EXPAND, SD_FOCUS = 0, 1, 2
 
 _i32 = ctypes.c_int32
 
@@ -53,6 +55,12 @@ class CopyDesc(ctypes.Structure):
     _fields_ = [(n, _i32) for n in (
         "n", "h", "w", "c", "in_c_off", "in_c_stride",
         "out_c_off", "out_c_stride", "scale", "dtype", "out_layout")] + [("dequant", ctypes.c_float)]
+
+
+class DepthDesc(ctypes.Structure):
+    _fields_ = [(n, _i32) for n in (
+        "n", "h", "w", "c", "in_c_off", "in_c_stride",
+        "ho", "wo", "out_c_off", "out_c_stride", "gain", "mode", "dtype")]
 
 
 class DecodeDesc(ctypes.Structure):
@@ -92,7 +100,7 @@ class _HeadOp(ctypes.Structure):
 
 class _OpUnion(ctypes.Union):
     _fields_ = [("conv", ConvDesc), ("pool", PoolDesc), ("copy", CopyDesc), ("pair", ConvDesc * 2),
-                ("head", _HeadOp)]
+                ("head", _HeadOp), ("depth", DepthDesc)]
 
 
 class Op(ctypes.Structure):
@@ -150,6 +158,7 @@ _SIGS = [
                                     _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     ("ycx_maxpool", _i32, [ctypes.POINTER(PoolDesc), _VP, _VP, _VP]),
     ("ycx_copy_channels", _i32, [ctypes.POINTER(CopyDesc), _VP, _VP, _VP]),
+    ("ycx_space_depth", _i32, [ctypes.POINTER(DepthDesc), _VP, _VP, _VP]),
     ("ycx_quantize_fp8", _i32, [_VP, _VP, ctypes.c_int64, ctypes.c_float, _VP]),
     ("ycx_decode", _i32, [ctypes.POINTER(DecodeDesc), _VP, _VP, _VP]),
     ("ycx_filter_decoded", _i32, [ctypes.POINTER(FilterDesc), _VP, _VP, _VP, _VP, _VP]),

@@ -11,8 +11,9 @@ Lowering (once per input shape / device / precision):
    depthwise 5x5 + concat with Ghost's shortcut (``ghost``), max-pool, upsample, concat, Detect/IDetect heads.
 2. Passes: nearest-x2 upsample fused into its producing conv's store
    (YCX_OUT_NHWC_UP2); the SPPCSPC 5/9/13 pools run as a k5 cascade (exact for
-   max with -inf padding); every concat input that a kernel produces is written
-   straight into its channel slice of the concat buffer (Concat costs nothing;
+   max with -inf padding); Contract, Expand and a Focus that reads an activation move their pixels with
+   ycx_space_depth (``depth``; a Focus on the image is ReOrg + Conv: ``stem_reorg``); every concat
+   input that a kernel produces is written straight into its channel slice of the concat buffer (Concat costs nothing;
    a copy kernel runs only for inputs that cannot alias).
 3. Bind the schedule to memory: ``schedule.Schedule`` decides, without a device, which launches
    run the graph (stem pair, conv pair and trio, pooled 1x1, pool cascade) and which buffers
@@ -35,7 +36,8 @@ from torch import nn
 from . import _lib as L
 from . import pack
 from .nets.common import (SP, SPP, SPPCSPC, SPPF, MP, Bottleneck, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC,
-                          Concat, Conv, DownC, Ghost, GhostConv, ReOrg, RepConv, Res, RobustConv, RobustConv2)
+                          Concat, Contract, Conv, DownC, Expand, Focus, Ghost, GhostConv, ReOrg, RepConv, Res,
+                          RobustConv, RobustConv2)
 from .nets.detect import Detect, IAuxDetect, IDetect
 from .pack import pack_deconv_weights, pack_fp8_weights  # noqa: F401  (re-exported)
 from .schedule import Schedule, cascade_fits, cout_pad  # noqa: F401  (re-exported)
@@ -125,6 +127,10 @@ GCONV_K = (3, 5, 7, 11)
 GCONV_S = (1, 2, 4, 8)
 # what ycx_deconv2d takes: kernel == stride
 DECONV_S = (2, 4, 8)
+# what ycx_space_depth takes: the gain (Focus: 2), and the contiguous channel run a multiple of DEPTH_RUN
+DEPTH_GAIN = (2, 3, 4)
+DEPTH_RUN = 8
+DEPTH_NAME = {L.SD_CONTRACT: 'contract', L.SD_EXPAND: 'expand', L.SD_FOCUS: 'focus'}
 
 
 class Graph:
@@ -238,6 +244,35 @@ class Graph:
                              f"fails there)")
         return Val(x.n, x.h // 2, x.w // 2, 4 * x.c, role='reorg')
 
+    def depth(self, x: Val, mode, gain):
+        """Contract / Expand (nets/common.py:787-812), or the pixel-phase concat of a Focus that reads an
+        activation (:767), as a node of its own kind, 'depth' (ycx_space_depth): a pure move, so the
+        concat-slice aliasing takes it and an fp8 plan ties its input and output to one scale."""
+        what = DEPTH_NAME[mode].capitalize()
+        if x.role in ('input', 'reorg'):
+            raise NotImplementedError(f"ycx: {what} on the model input (ycx_space_depth reads an NHWC activation, "
+                                      f"not the image; a Focus there is lowered into ycx_stem_conv_reorg)")
+        limits = (f"ycx_space_depth takes a gain in {DEPTH_GAIN} (Focus: 2) and a contiguous channel run (c for "
+                  f"Contract and Focus, c / gain^2 for Expand) that is a multiple of {DEPTH_RUN}")
+        if isinstance(gain, bool) or not isinstance(gain, int) or gain not in DEPTH_GAIN or \
+                (mode == L.SD_FOCUS and gain != 2):
+            raise NotImplementedError(f"ycx: {what} with gain {gain!r} has no HIP kernel: {limits}")
+        ss = gain * gain
+        if mode == L.SD_EXPAND:
+            if x.c % ss:
+                raise ValueError(f"ycx: Expand({gain}) needs channels divisible by {ss}, got {x.c} (the reference's "
+                                 f"view fails there)")
+            out, run = Val(x.n, x.h * gain, x.w * gain, x.c // ss), x.c // ss
+        else:
+            if x.h % gain or x.w % gain:
+                raise ValueError(f"ycx: {what}({gain}) needs spatial sides divisible by {gain}, got {x.h} x {x.w} "
+                                 f"(the reference's view fails there)")
+            out, run = Val(x.n, x.h // gain, x.w // gain, x.c * ss), x.c
+        if run % DEPTH_RUN:
+            raise NotImplementedError(f"ycx: {what}({gain}) on {x.c} channels (a run of {run}) has no HIP kernel: "
+                                      f"{limits}")
+        return self.add('depth', [x], out, mode=mode, gain=gain)
+
     def upsample(self, x: Val):
         return self.add('up', [x], Val(x.n, 2 * x.h, 2 * x.w, x.c))
 
@@ -272,6 +307,19 @@ def ghostconv_module(g: Graph, m: GhostConv, x: Val, residual=None):
     y = conv_module(g, m.cv1, x)
     w, b = fold_bn(c.weight, m.cv2.bn)
     return g.ghost(y, w, b, act_of(m.cv2.act), residual=residual)
+
+
+def focus_module(g: Graph, m: Focus, x: Val):
+    """Focus (nets/common.py:759-767): its four pixel phases come in ReOrg's order, so on the image it is
+    ReOrg + Conv, the ``stem_reorg`` node; on an activation a 'depth' node in focus mode, then the conv."""
+    if x.role != 'input':
+        return conv_module(g, m.conv, g.depth(x, L.SD_FOCUS, 2))
+    c = m.conv.conv
+    k, s, p = _square(c.kernel_size, 'kernel'), _square(c.stride, 'stride'), _square(c.padding, 'padding')
+    if not (k == 3 and p == 1 and s in (1, 2) and c.groups == 1 and _pair(c.dilation) == (1, 1)):
+        raise NotImplementedError("ycx: Focus on the model input is lowered into ycx_stem_conv_reorg, which takes a "
+                                  f"3x3 / pad-1 conv of stride 1 or 2 with groups 1; got k{k} s{s} p{p} g{c.groups}")
+    return conv_module(g, m.conv, g.reorg(x))
 
 
 def conv_or_ghost(g: Graph, m, x: Val):
@@ -398,6 +446,12 @@ def lower_module(g: Graph, m, x):
         return pool_module(g, m.m, x)
     if isinstance(m, ReOrg):
         return g.reorg(x)
+    if isinstance(m, Focus):
+        return focus_module(g, m, x)
+    if isinstance(m, Contract):
+        return g.depth(x, L.SD_CONTRACT, m.gain)
+    if isinstance(m, Expand):
+        return g.depth(x, L.SD_EXPAND, m.gain)
     if isinstance(m, DownC):  # nets/common.py:181-182
         y1 = conv_module(g, m.cv2, conv_module(g, m.cv1, x))
         return g.concat([y1, conv_module(g, m.cv3, pool_module(g, m.mp, x))])
@@ -587,7 +641,8 @@ class Plan:
             copies, off = [], 0
             for v in node.inputs:
                 if v.buf is None and v.role == 'act' and v.producer is not None and \
-                        v.producer.kind in ('conv', 'stem', 'stem_reorg', 'gconv', 'deconv', 'ghost', 'pool', 'up'):
+                        v.producer.kind in ('conv', 'stem', 'stem_reorg', 'gconv', 'deconv', 'ghost', 'pool', 'up',
+                                            'depth'):
                     v.buf, v.coff = out.buf, off
                 else:
                     copies.append((v, off))
@@ -689,7 +744,7 @@ class Engine:
 
     def _assign_fp8_scales(self, amax):
         """One power-of-two scale per group of buffers tied by a pool or a copy
-        (max-pool, nearest upsample and concat copies move bytes unchanged):
+        (max-pool, nearest upsample, concat copies and space/depth moves leave bytes unchanged):
         s = 2^floor(log2(224 / amax)), i.e. the calibrated max lands in
         [224, 448) with 2x headroom below the e4m3 limit. Power-of-two scales
         make every rescale exact."""
@@ -704,7 +759,7 @@ class Engine:
                 i = parent[i]
             return i
         for nd in self.graph.nodes:
-            if nd.kind in ('pool', 'up', 'concat'):
+            if nd.kind in ('pool', 'up', 'concat', 'depth'):
                 ins = [v for v in nd.inputs if v.buf is not None]
                 if nd.out.buf is None:
                     continue
@@ -771,6 +826,7 @@ class Engine:
                 'gconv': lambda la: self._plain_op(la.nodes[0], L.OP_GCONV, 'gconv_g{g}_k{k}s{s}'),
                 'deconv': lambda la: self._plain_op(la.nodes[0], L.OP_DECONV, 'deconv_s{s}'),
                 'ghost': lambda la: self._plain_op(la.nodes[0], L.OP_GHOST, 'ghost_dw'),
+                'depth': lambda la: self._depth_op(la.nodes[0]),
                 'pool': lambda la: self._pool_op(la.nodes[0], levels=la.levels),
                 'copy': lambda la: self._copy_op(la.src, la.dst, la.off, la.scale, nchw=la.nchw)}
         ops = [emit[la.kind](la) for la in self.schedule.launches]
@@ -914,6 +970,25 @@ class Engine:
         name = f"maxpool_k{p['k']}s{p['s']}" + (f"_cascade{levels}" if levels > 1 else "")
         self.op_info.append(dict(kind='pool', name=name, flops=0,
                                  bytes=(x.n * (x.h * x.w + levels * out.h * out.w) * x.c * self.dtype.itemsize)))
+        return op
+
+    def _depth_op(self, node):
+        """One OP_DEPTH (ycx_space_depth): the node's input slice moved into its output slice."""
+        x, out, p = node.inputs[0], node.out, node.p
+        d = L.DepthDesc()
+        d.n, d.h, d.w, d.c, d.in_c_off, d.in_c_stride = x.n, x.h, x.w, x.c, x.coff, x.buf.c
+        d.ho, d.wo, d.out_c_off, d.out_c_stride = out.h, out.w, out.coff, out.buf.c
+        d.gain, d.mode, d.dtype = p['gain'], p['mode'], self.dt
+        if any(v % DEPTH_RUN for v in (d.in_c_off, d.in_c_stride, d.out_c_off, d.out_c_stride)):
+            raise NotImplementedError(f"ycx: {DEPTH_NAME[p['mode']]} between channel slices at {d.in_c_off} of "
+                                      f"{d.in_c_stride} and {d.out_c_off} of {d.out_c_stride}: ycx_space_depth takes "
+                                      f"offsets and strides that are multiples of {DEPTH_RUN}")
+        op = L.Op()
+        op.kind = L.OP_DEPTH
+        op.d.depth = d
+        op.in_, op.out = x.buf.tensor.data_ptr(), out.buf.tensor.data_ptr()
+        self.op_info.append(dict(kind='depth', name=f"{DEPTH_NAME[p['mode']]}{p['gain']}", flops=0,
+                                 bytes=2 * x.n * x.h * x.w * x.c * self.dtype.itemsize))
         return op
 
     def _copy_op(self, x, out, off, scale, nchw=False):
@@ -1104,6 +1179,11 @@ class Engine:
             shift('in_', d.h * d.w * d.in_c_stride * es)
             shift('out', d.ho * d.wo * d.out_c_stride * es)
             d.n = k
+        elif o.kind == L.OP_DEPTH:
+            d = o.d.depth
+            shift('in_', d.h * d.w * d.in_c_stride * es)
+            shift('out', d.ho * d.wo * d.out_c_stride * es)
+            d.n = k
         elif o.kind == L.OP_COPY:
             d = o.d.copy
             shift('in_', d.h * d.w * d.in_c_stride * es)
@@ -1124,6 +1204,8 @@ class Engine:
             return op.d.pair[1].ho
         if op.kind == L.OP_POOL:
             return op.d.pool.ho
+        if op.kind == L.OP_DEPTH:
+            return op.d.depth.ho
         return op.d.copy.h * op.d.copy.scale
 
     def _exec_ops(self):

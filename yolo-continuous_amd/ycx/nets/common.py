@@ -121,6 +121,35 @@ class ReOrg(_Holder):
     engine folds it into the operand gather of the Conv that reads it (ycx_stem_conv_reorg)."""
 
 
+class Focus(_Holder):
+    """conv(cat of the four pixel phases of x), x(b, c, 2h, 2w) -> (b, c2, h, w): the phases in ReOrg's
+    order, then a Conv(4 c1, c2, k, s, p, g, act) (nets/common.py:759-767). On the image the engine
+    folds the regrouping into that conv's gather (ycx_stem_conv_reorg); on an activation it runs
+    ycx_space_depth in focus mode."""
+
+    def __init__(self, c1, c2, k=1, s=1, p=None, g=1, act=True):
+        super().__init__()
+        self.conv = Conv(c1 * 4, c2, k, s, p, g, act)
+
+
+class Contract(_Holder):
+    """Width-height into channels, x(b, c, h, w) -> (b, c s^2, h/s, w/s), channel (a s + b) c + i from
+    pixel phase (a, b) (nets/common.py:787-798). No parameters; ycx_space_depth."""
+
+    def __init__(self, gain=2):
+        super().__init__()
+        self.gain = gain
+
+
+class Expand(_Holder):
+    """Channels into width-height, x(b, c, h, w) -> (b, c / s^2, h s, w s), Contract's inverse
+    (nets/common.py:801-812). No parameters; ycx_space_depth."""
+
+    def __init__(self, gain=2):
+        super().__init__()
+        self.gain = gain
+
+
 class Concat(_Holder):
     """Channel concat (nets/common.py:54-60); never materialised on device."""
 

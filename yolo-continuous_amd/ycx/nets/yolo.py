@@ -26,9 +26,9 @@ from torch import nn
 
 from ..utils.helper_io import cvt_cfg
 from .common import (SP, SPP, SPPCSPC, SPPF, MP, Bottleneck, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC,
-                     Concat, Conv, DownC, Ghost, GhostConv, GhostCSPA, GhostCSPB, GhostCSPC, GhostSPPCSPC, ImplicitA,
-                     ImplicitM, ReOrg, RepConv, Res, ResCSPA, ResCSPB, ResCSPC, ResX, ResXCSPA, ResXCSPB, ResXCSPC,
-                     RobustConv, RobustConv2, dw_conv)
+                     Concat, Contract, Conv, DownC, Expand, Focus, Ghost, GhostConv, GhostCSPA, GhostCSPB, GhostCSPC,
+                     GhostSPPCSPC, ImplicitA, ImplicitM, ReOrg, RepConv, Res, ResCSPA, ResCSPB, ResCSPC, ResX, ResXCSPA,
+                     ResXCSPB, ResXCSPC, RobustConv, RobustConv2, dw_conv)
 from .detect import Detect, IAuxDetect, IDetect
 
 
@@ -49,12 +49,13 @@ _MODULES = {
     'ResXCSPA': ResXCSPA, 'ResXCSPB': ResXCSPB, 'ResXCSPC': ResXCSPC,
     'GhostConv': GhostConv, 'Ghost': Ghost, 'GhostCSPA': GhostCSPA, 'GhostCSPB': GhostCSPB, 'GhostCSPC': GhostCSPC,
     'GhostSPPCSPC': GhostSPPCSPC,
+    'Focus': Focus, 'Contract': Contract, 'Expand': Expand,
 }
 # Reference modules constructible by its parse_model but used by neither shipped
 # YAML: named here so the error says "out of scope", not "unknown".
 _OUT_OF_SCOPE = {
     'Chuncat', 'Shortcut', 'Foldcut', 'Stem',
-    'GhostStem', 'Focus', 'Contract', 'Expand', 'Classify',
+    'GhostStem', 'Classify',
     'TransformerLayer', 'TransformerBlock', 'IBin', 'RepBottleneck',
 } | {f'{p}{s}' for p in ('RepRes', 'RepResX', 'RepBottleneck')
      for s in ('CSPA', 'CSPB', 'CSPC')}
@@ -64,7 +65,7 @@ _GHOST_LIKE = (GhostConv, Ghost, GhostCSPA, GhostCSPB, GhostCSPC, GhostSPPCSPC)
 
 _CONV_LIKE = (nn.Conv2d, Conv, RobustConv, RobustConv2, dw_conv, RepConv, DownC, SPP, SPPF, SPPCSPC, Bottleneck,
               BottleneckCSPA, BottleneckCSPB, BottleneckCSPC, Res, ResCSPA, ResCSPB, ResCSPC, ResX, ResXCSPA, ResXCSPB,
-              ResXCSPC, GhostConv, Ghost, GhostCSPA, GhostCSPB, GhostCSPC, GhostSPPCSPC)
+              ResXCSPC, GhostConv, Ghost, GhostCSPA, GhostCSPB, GhostCSPC, GhostSPPCSPC, Focus)
 _CSP_LIKE = (DownC, SPPCSPC, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC, ResCSPA, ResCSPB, ResCSPC, ResXCSPA,
              ResXCSPB, ResXCSPC, GhostCSPA, GhostCSPB, GhostCSPC, GhostSPPCSPC)
 _ACTS = {'LeakyReLU': nn.LeakyReLU, 'SiLU': nn.SiLU, 'Identity': nn.Identity}
@@ -133,6 +134,10 @@ def parse_model(d, ch, anchors, num_classes):
                 args[1] = [list(range(args[1] * 2))] * len(f)
         elif m is ReOrg:
             c2 = ch[f] * 4
+        elif m is Contract:
+            c2 = ch[f] * args[0] ** 2
+        elif m is Expand:
+            c2 = ch[f] // args[0] ** 2
         else:
             c2 = ch[f]
         m_ = nn.Sequential(*[m(*args) for _ in range(n)]) if n > 1 else m(*args)

@@ -28,6 +28,7 @@ class Launch:
     gconv      nodes (gconv,)
     deconv     nodes (deconv,)
     ghost      nodes (ghost,)
+    depth      nodes (depth,): one ycx_space_depth move (Contract, Expand, Focus on an activation)
     pool       nodes: the cascade's pools, ``levels`` of them
     copy       nodes (up | concat | tonchw,): ``src`` -> channels from ``off`` of ``dst``, upsampled
                by ``scale`` (1 or 2), ``nchw``: to the fp32 NCHW output
@@ -250,7 +251,7 @@ class Schedule:
                 add('conv_pair', nd, pairs[i], *trio, store_a=len(nd.out.consumers) > 1 and not trio)
             elif k in ('conv', 'stem', 'stem_reorg'):
                 add('conv', nd, *([pooled[i]] if i in pooled else []))
-            elif k in ('gconv', 'deconv', 'ghost'):
+            elif k in ('gconv', 'deconv', 'ghost', 'depth'):
                 add(k, nd)
             elif k == 'pool':
                 chain = cascades.get(i, [nd])
