@@ -35,6 +35,8 @@
  *   ycx_conv2d_head     Detect head conv (one level) fused with  nets/detect.py:27-38 +
  *                       decode_box + the candidate filter        detect.py:29-121
  *   ycx_idetect_decode  IDetect eval branch (strides supplied)  nets/idetect.py:33-45
+ *   ycx_ibin_decode     IBin eval branch (strides supplied)     nets/ibin.py:48-72,
+ *                                                                losses/sigmoid_bin.py:49-63
  *   ycx_sort_nms        per-class torchvision.ops.nms loop      detect.py:124-137
  *   ycx_run_ops         Model.forward layer loop                nets/yolo.py:143-153
  *   ycx_letterbox       image -> network input                   detect.py:16-26,
@@ -495,6 +497,26 @@ ycx_status ycx_decode(const ycx_decode_desc* d, const float* head, float* out, v
  * supplies it. */
 ycx_status ycx_idetect_decode(const ycx_decode_desc* d, float stride, const float* head, float* z, float* xview,
                               void* stream);
+/* IBin's eval outputs for one level (nets/ibin.py:48-72): as ycx_idetect_decode, but width and
+ * height come from SigmoidBin.forward (losses/sigmoid_bin.py:49-63) instead of (sigmoid*2)^2.
+ * d->no is the raw width nc + 3 + 2*(bin_count + 1): x, y, then for w and for h one regression
+ * logit and bin_count bin logits, then objectness and the classes. head: fp32 NCHW
+ * [n][na*no][h][w]; xview gets the raw map as (n, na, h, w, no); z [n][rows_total][nc + 5] gets,
+ * at row_off, rows in (a, y, x) order with p = sigmoid(raw):
+ *   xy = (p*2 - 0.5 + grid) * stride
+ *   w  = clamp((p[2]*2 - 1) * (float)(4.0/21) + w_bins[argmax p[3..23]], 0, 4) * anchor_w
+ *   h  = the same from p[24], p[25..45] and h_bins, times anchor_h
+ *   z[4..] = p[46..]
+ * The arg-max is torch.max's: the first index of the maximum of the sigmoid'd scores.
+ * w_bins, h_bins: HOST arrays of bin_count floats (the modules' `bins` buffers), copied into the
+ * kernel's arguments. d->anchors_scaled holds the level's anchor_grid in pixels. Cells per block
+ * are derived from no so that the two LDS tiles stay inside 64 KB.
+ * The descriptor is judged before the data pointers. YCX_ERR_BAD_ARG: a null descriptor, a
+ * non-positive size or bin_count, no <= 2*(bin_count+1) + 3 (no class), row_off < 0 or
+ * row_off + na*h*w > rows_total, a null pointer. YCX_ERR_UNSUPPORTED: bin_count != 21 (the
+ * reference's eval slices are written out for 21 bins), na > 8, no > 256, n > 65535. */
+ycx_status ycx_ibin_decode(const ycx_decode_desc* d, float stride, int32_t bin_count, const float* w_bins,
+                           const float* h_bins, const float* head, float* z, float* xview, void* stream);
 /* Candidate outputs of both filters:
  *   cand        [n][rows] ycx_cand, written only at the rows that pass (dense by row)
  *   cand_rows   [n][rows] int32, the passing row indices, compacted (any order)

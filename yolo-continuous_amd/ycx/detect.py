@@ -199,6 +199,39 @@ def idetect_outputs(head, outs, input_hw):
     return z, xs
 
 
+def ibin_outputs(head, outs, input_hw):
+    """IBin's eval return value (nets/ibin.py:48-74) from the engine's raw head maps (NCHW fp32,
+    one per level): (z [n, sum na*ny*nx, nc + 5] decoded in pixels, [x_i (n, na, ny, nx, no)]),
+    one ycx_ibin_decode per level on the current stream. Anchors come from ``anchor_grid``, the
+    bin centres from the two SigmoidBin children's ``bins``. The reference leaves IBin.stride
+    unset as it does IDetect's; unless head.stride is given, stride_i = input height / ny_i
+    (the same documented deviation)."""
+    n, na, no, nc, bc = outs[0].shape[0], head.na, head.no, head.nc, head.bin_count
+    dev = outs[0].device
+    rows = sum(na * o.shape[2] * o.shape[3] for o in outs)
+    z = torch.empty((n, rows, nc + 5), dtype=torch.float32, device=dev)
+    xs, off = [], 0
+    grid_anchors = head.anchor_grid.detach().to('cpu', torch.float32).reshape(len(outs), na, 2)
+    bins = [(ctypes.c_float * bc)(*b.bins.detach().to('cpu', torch.float32).tolist())
+            for b in (head.w_bin_sigmoid, head.h_bin_sigmoid)]
+    st = L.stream_handle(dev)
+    for i, o in enumerate(outs):
+        ny, nx = int(o.shape[2]), int(o.shape[3])
+        if o.shape[1] != na * no:
+            raise ValueError(f"ycx: IBin level {i} has {o.shape[1]} channels, expected {na}*{no}")
+        stride = float(head.stride[i]) if head.stride is not None else float(np.float32(input_hw[0]) / np.float32(ny))
+        d = L.DecodeDesc()
+        d.n, d.h, d.w, d.na, d.no, d.rows_total, d.row_off = n, ny, nx, na, no, rows, off
+        for a in range(na):
+            d.anchors_scaled[2 * a], d.anchors_scaled[2 * a + 1] = float(grid_anchors[i, a, 0]), float(grid_anchors[i, a, 1])
+        xv = torch.empty((n, na, ny, nx, no), dtype=torch.float32, device=dev)
+        L.check(L.lib.ycx_ibin_decode(ctypes.byref(d), ctypes.c_float(stride), bc, bins[0], bins[1],
+                                      o.contiguous().data_ptr(), z.data_ptr(), xv.data_ptr(), st), "ycx_ibin_decode")
+        xs.append(xv)
+        off += na * ny * nx
+    return z, xs
+
+
 class DevicePost:
     """decode_box + non_max_suppression on device for fixed head shapes
     (``detect.py:29-144``): ycx_decode_filter -> ycx_sort_nms on the current

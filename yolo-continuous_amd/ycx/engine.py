@@ -38,7 +38,7 @@ from . import pack
 from .nets.common import (SP, SPP, SPPCSPC, SPPF, MP, Bottleneck, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC,
                           Concat, Contract, Conv, DownC, Expand, Focus, Ghost, GhostConv, ReOrg, RepConv, Res,
                           RobustConv, RobustConv2)
-from .nets.detect import Detect, IAuxDetect, IDetect
+from .nets.detect import Detect, IAuxDetect, IBin, IDetect
 from .pack import pack_deconv_weights, pack_fp8_weights  # noqa: F401  (re-exported)
 from .schedule import Schedule, cascade_fits, cout_pad  # noqa: F401  (re-exported)
 
@@ -519,7 +519,9 @@ def lower_module(g: Graph, m, x):
             b = conv.bias.detach().to('cpu', torch.float64)
             outs.append(g.conv(x[idx], w, b, 1, 1, 0, head=True))
         return outs
-    if isinstance(m, IDetect):  # IAuxDetect too: its eval uses the main heads only (x[:nl])
+    # IAuxDetect too: its eval uses the main heads only (x[:nl]); IBin: the same convs at its own width
+    # (nets/ibin.py:46-47), the binned w/h decode reads their fp32 logits (ycx_ibin_decode)
+    if isinstance(m, (IDetect, IBin)):
         outs = []
         for i in range(m.nl):
             conv = m.m[i]

@@ -29,7 +29,7 @@ from .common import (SP, SPP, SPPCSPC, SPPF, MP, Bottleneck, BottleneckCSPA, Bot
                      Concat, Contract, Conv, DownC, Expand, Focus, Ghost, GhostConv, GhostCSPA, GhostCSPB, GhostCSPC,
                      GhostSPPCSPC, ImplicitA, ImplicitM, ReOrg, RepConv, Res, ResCSPA, ResCSPB, ResCSPC, ResX, ResXCSPA,
                      ResXCSPB, ResXCSPC, RobustConv, RobustConv2, dw_conv)
-from .detect import Detect, IAuxDetect, IDetect
+from .detect import Detect, IAuxDetect, IBin, IDetect
 
 
 def make_divisible(x, divisor):
@@ -41,6 +41,7 @@ _MODULES = {
     'Bottleneck': Bottleneck, 'BottleneckCSPA': BottleneckCSPA, 'BottleneckCSPB': BottleneckCSPB,
     'BottleneckCSPC': BottleneckCSPC, 'SPP': SPP, 'SPPF': SPPF, 'ImplicitA': ImplicitA,
     'ImplicitM': ImplicitM, 'Detect': Detect, 'IDetect': IDetect, 'IAuxDetect': IAuxDetect,
+    'IBin': IBin,
     'nn.Conv2d': nn.Conv2d, 'nn.BatchNorm2d': nn.BatchNorm2d, 'nn.Upsample': nn.Upsample,
     'ReOrg': ReOrg, 'DownC': DownC,
     'dw_conv': dw_conv, 'RobustConv': RobustConv, 'RobustConv2': RobustConv2, 'Res': Res, 'ResX': ResX,
@@ -56,7 +57,7 @@ _MODULES = {
 _OUT_OF_SCOPE = {
     'Chuncat', 'Shortcut', 'Foldcut', 'Stem',
     'GhostStem', 'Classify',
-    'TransformerLayer', 'TransformerBlock', 'IBin', 'RepBottleneck',
+    'TransformerLayer', 'TransformerBlock', 'RepBottleneck',
 } | {f'{p}{s}' for p in ('RepRes', 'RepResX', 'RepBottleneck')
      for s in ('CSPA', 'CSPB', 'CSPC')}
 # The Ghost family runs on ycx_ghost_dw, which reads an NHWC activation: none of them can take the
@@ -128,7 +129,7 @@ def parse_model(d, ch, anchors, num_classes):
             args = [ch[f]]
         elif m is Concat:
             c2 = sum(ch[x] for x in f)
-        elif m in (Detect, IDetect, IAuxDetect):
+        elif m in (Detect, IDetect, IAuxDetect, IBin):
             args.append([ch[x] for x in f])
             if isinstance(args[1], int):
                 args[1] = [list(range(args[1] * 2))] * len(f)
@@ -248,6 +249,9 @@ class Model(nn.Module):
             self.set_precision('bf16')
             return self.forward(x)
         head = self.model[-1]
+        if isinstance(head, IBin):  # eval branch: (z, x) as nets/ibin.py:74, z rows nc + 5 wide
+            from ..detect import ibin_outputs
+            return ibin_outputs(head, outs, x.shape[2:])
         if isinstance(head, IDetect):  # eval branch: (z, x[:nl]) as nets/idetect.py:45, nets/iaux_detect.py:49
             from ..detect import idetect_outputs
             return idetect_outputs(head, outs, x.shape[2:])
