@@ -29,6 +29,8 @@
  *                       Concat (only when a slice cannot alias)  nets/common.py:54-60
  *   ycx_space_depth     Contract, Expand                         nets/common.py:787-812
  *                       Focus's pixel-phase cat on an activation nets/common.py:767
+ *   ycx_classify        Classify: AdaptiveAvgPool2d(1) + Conv2d  nets/common.py:815-825
+ *                       (its centre tap) + Flatten
  *   ycx_decode          decode_box (one head level)             detect.py:29-87
  *   ycx_filter_decoded  non_max_suppression lines 98-121        detect.py:98-121
  *   ycx_decode_filter   decode_box + the same filter, fused     detect.py:29-121
@@ -61,7 +63,8 @@ extern "C" {
  * (ycx_struct_size, ids 0 to 11 unchanged) at load time; a zero-initialised descriptor
  * means what it meant before. ycx_space_depth / YCX_OP_DEPTH add ycx_depth_desc, a new member of
  * ycx_op's union that is smaller than `pair`, so sizeof(ycx_op) and the ids 0 to 11 stay as they are;
- * the new struct has no id (the ctypes mirror is checked through sizeof(ycx_op)). */
+ * the new struct has no id (the ctypes mirror is checked through sizeof(ycx_op)). ycx_classify /
+ * YCX_OP_CLASSIFY add ycx_classify_desc in the same way: a union member smaller than `pair`, no id. */
 #define YCX_ABI_VERSION 9
 
 typedef int32_t ycx_status;
@@ -187,6 +190,15 @@ typedef struct ycx_depth_desc {
   int32_t dtype;            /* YCX_DT_*: moved as bytes                             */
 } ycx_depth_desc;
 
+/* Global average pool + dense layer over an NHWC channel slice (ycx_classify, below). n, h, w, c describe
+ * the input slice; the output is fp32 [n][cout]. */
+typedef struct ycx_classify_desc {
+  int32_t n, h, w, c, in_c_off, in_c_stride;
+  int32_t cout;
+  int32_t dtype;            /* YCX_DT_*: the input's element type                   */
+  float dequant;            /* YCX_DT_FP8: 1 / s_in, as ycx_copy_desc (else unused) */
+} ycx_classify_desc;
+
 /* Decode of one head level (detect.py:29-87 semantics). head is fp32 NCHW
  * [n][na*no][h][w]; out is fp32 [n][rows_total][no], written at row_off.
  * anchors_scaled[2a], [2a+1] = anchor_w/stride_w, anchor_h/stride_h computed in
@@ -272,7 +284,8 @@ enum { YCX_OP_CONV = 1, YCX_OP_STEM = 2, YCX_OP_POOL = 3, YCX_OP_COPY = 4, YCX_O
        YCX_OP_GCONV = 9 /* ycx_conv2d_grouped: d.conv, in, weight (fp32), bias, out, residual */,
        YCX_OP_DECONV = 10 /* ycx_deconv2d: d.conv, in, weight, bias, out */,
        YCX_OP_GHOST = 11 /* ycx_ghost_dw: d.conv, in, weight (fp32), bias, out, residual */,
-       YCX_OP_DEPTH = 12 /* ycx_space_depth: d.depth, in, out */ };
+       YCX_OP_DEPTH = 12 /* ycx_space_depth: d.depth, in, out */,
+       YCX_OP_CLASSIFY = 13 /* ycx_classify: d.classify, in, weight (fp32), bias, out, workspace */ };
 typedef struct ycx_op {
   int32_t kind;
   int32_t pad_;
@@ -281,6 +294,7 @@ typedef struct ycx_op {
     ycx_pool_desc pool;
     ycx_copy_desc copy;
     ycx_depth_desc depth;   /* DEPTH                                                 */
+    ycx_classify_desc classify;  /* CLASSIFY                                         */
     ycx_conv_desc pair[2];  /* STEM2: [0] the stem, [1] the stride-2 conv it feeds;
                                CONV_PAIR: [0] the first 1x1 conv, [1] the 1x1 conv reading it */
     struct {
@@ -300,7 +314,8 @@ typedef struct ycx_op {
   int32_t* cand_counts;     /* HEAD: [n], zeroed before the first level's op        */
   int32_t* status;          /* HEAD (nullable): the range guard flag, below         */
   void* out2;               /* CONV_PAIR: the second conv's output (out: the first's, nullable) */
-  void* workspace;          /* CONV with d.conv.k_split > 1: fp32 partials, >= ycx_conv_workspace_size */
+  void* workspace;          /* CONV with d.conv.k_split > 1: fp32 partials, >= ycx_conv_workspace_size;
+                               CLASSIFY: fp32 [n][c], the pooled means                */
   /* CONV_PAIR with out3 set: ycx_conv2d_pair_pool, the pair plus the pooled 1x1 `conv3` */
   ycx_conv_desc conv3;
   const void* weight3;      /* conv3's packed weights                               */
@@ -484,6 +499,29 @@ ycx_status ycx_copy_channels(const ycx_copy_desc* d, const void* x, void* y, voi
  * multiple of 8, an unknown dtype or mode. The descriptor is judged before the data pointers, as in
  * ycx_conv2d_grouped. */
 ycx_status ycx_space_depth(const ycx_depth_desc* d, const void* x, void* y, void* stream);
+/* Classify (nets/common.py:815-825) on an NHWC activation: AdaptiveAvgPool2d(1), the Conv2d on the 1 x 1
+ * map it leaves, Flatten. With an odd kernel and p == k // 2 only the centre tap of that conv meets data, so
+ * the layer is  y[n, o] = bias[o] + sum_c w[o, c] * mean_hw x[n, :, :, c].
+ *   x          the channel slice [in_c_off, in_c_off + c) of an NHWC buffer with in_c_stride channels,
+ *              dtype bf16 / fp16 / f32 / fp8 (e4m3; the mean is multiplied by d->dequant = 1 / s_in)
+ *   w          fp32 [cout][c], the centre tap, in every precision (as ycx_conv2d_grouped's weights)
+ *   bias       fp32 [cout], nullable
+ *   y          fp32 [n][cout]
+ *   workspace  fp32 [n][c]: receives the pooled means
+ * Two launches on the stream, one op. The pool: each lane reads 16 bytes of consecutive channels (8 bytes
+ * for an e4m3 slice on 8- but not 16-channel bounds), a block of 256 threads covers CL channel vectors
+ * x 256 / CL pixel phases, every lane sums its pixels in fp32 in ascending order, the phases are combined
+ * through LDS in ascending order, then one IEEE division by h * w. The linear step: one wave per output
+ * and up to eight images, lanes over c with 16-byte loads, fp32 FMAs, a fixed xor-butterfly over the
+ * lanes. No atomics: two runs on the same input give the same bits. The launch sizes are functions of the
+ * descriptor alone.
+ * YCX_ERR_BAD_ARG before any device call: a null descriptor, x, w, y or workspace; an unknown dtype;
+ * n, h, w, c or cout <= 0; c, in_c_off or in_c_stride no multiple of 8; in_c_off < 0 or
+ * in_c_off + c > in_c_stride.
+ * YCX_ERR_UNSUPPORTED, also before any device call: h * w >= 2^24 (the divisor and the pixel index stay exact),
+ * more than 2^31 - 1 pool blocks, or n > 8 * 65535 (the linear step's grid). */
+ycx_status ycx_classify(const ycx_classify_desc* d, const void* x, const float* w, const float* bias, float* y,
+                        float* workspace, void* stream);
 /* fp32 -> OCP e4m3fn bytes: y[i] = e4m3(clamp(x[i] * scale, +-448)), round to
  * nearest even: the exact cast of the YCX_DT_FP8 epilogues (calibration checks). */
 ycx_status ycx_quantize_fp8(const float* x, void* y, int64_t n, float scale, void* stream);

@@ -427,6 +427,7 @@ extern "C" ycx_status ycx_quantize_fp8(const float* x, void* y, int64_t n, float
 // ---------------------------------------------------------------------------
 // ycx_depth_desc joined the op's union without growing it (ycx.h: the ABI version and ycx_struct_size(8) stay)
 static_assert(sizeof(ycx_depth_desc) <= sizeof(ycx_conv_desc[2]), "ycx_depth_desc must not grow ycx_op's union");
+static_assert(sizeof(ycx_classify_desc) <= sizeof(ycx_conv_desc[2]), "ycx_classify_desc must not grow ycx_op's union");
 
 static ycx_status run_one(const ycx_op& op, void* stream) {
   switch (op.kind) {
@@ -450,6 +451,9 @@ static ycx_status run_one(const ycx_op& op, void* stream) {
       return ycx_copy_channels(&op.d.copy, op.in, op.out, stream);
     case YCX_OP_DEPTH:
       return ycx_space_depth(&op.d.depth, op.in, op.out, stream);
+    case YCX_OP_CLASSIFY:
+      return ycx_classify(&op.d.classify, op.in, (const float*)op.weight, op.bias, (float*)op.out,
+                          (float*)op.workspace, stream);
     case YCX_OP_STEM2:
       return ycx_stem_conv2(&op.d.pair[0], &op.d.pair[1], (const float*)op.in, (const float*)op.weight, op.bias,
                             op.weight2, op.bias2, op.out, stream);
@@ -498,8 +502,8 @@ extern "C" ycx_status ycx_set_trace(int32_t on) {
 
 static void trace_push(int32_t i, const ycx_op& op) {
   static const char* kinds[] = {"?", "conv", "stem", "pool", "copy", "stem2", "head", "conv_pair", "stem_reorg",
-                                "gconv", "deconv", "ghost", "depth"};
-  const char* k = (op.kind >= 1 && op.kind <= 12) ? kinds[op.kind] : kinds[0];
+                                "gconv", "deconv", "ghost", "depth", "classify"};
+  const char* k = (op.kind >= 1 && op.kind <= 13) ? kinds[op.kind] : kinds[0];
   char buf[160];
   if (op.kind == YCX_OP_CONV || op.kind == YCX_OP_STEM || op.kind == YCX_OP_HEAD || op.kind == YCX_OP_STEM2 ||
       op.kind == YCX_OP_CONV_PAIR || op.kind == YCX_OP_STEM_REORG || op.kind == YCX_OP_GCONV || op.kind == YCX_OP_DECONV ||

@@ -31,6 +31,7 @@ OP_GCONV = 9
 OP_DECONV = 10
 OP_GHOST = 11
 OP_DEPTH = 12
+OP_CLASSIFY = 13
 SD_CONTRACT, SD_EXPAND, SD_FOCUS = 0, 1, 2
 
 _i32 = ctypes.c_int32
@@ -61,6 +62,11 @@ class DepthDesc(ctypes.Structure):
     _fields_ = [(n, _i32) for n in (
         "n", "h", "w", "c", "in_c_off", "in_c_stride",
         "ho", "wo", "out_c_off", "out_c_stride", "gain", "mode", "dtype")]
+
+
+class ClassifyDesc(ctypes.Structure):
+    _fields_ = [(n, _i32) for n in ("n", "h", "w", "c", "in_c_off", "in_c_stride", "cout", "dtype")] + [
+        ("dequant", ctypes.c_float)]
 
 
 class DecodeDesc(ctypes.Structure):
@@ -100,7 +106,7 @@ class _HeadOp(ctypes.Structure):
 
 class _OpUnion(ctypes.Union):
     _fields_ = [("conv", ConvDesc), ("pool", PoolDesc), ("copy", CopyDesc), ("pair", ConvDesc * 2),
-                ("head", _HeadOp), ("depth", DepthDesc)]
+                ("head", _HeadOp), ("depth", DepthDesc), ("classify", ClassifyDesc)]
 
 
 class Op(ctypes.Structure):
@@ -161,6 +167,7 @@ _SIGS = [
     ("ycx_maxpool", _i32, [ctypes.POINTER(PoolDesc), _VP, _VP, _VP]),
     ("ycx_copy_channels", _i32, [ctypes.POINTER(CopyDesc), _VP, _VP, _VP]),
     ("ycx_space_depth", _i32, [ctypes.POINTER(DepthDesc), _VP, _VP, _VP]),
+    ("ycx_classify", _i32, [ctypes.POINTER(ClassifyDesc), _VP, _VP, _VP, _VP, _VP, _VP]),
     ("ycx_quantize_fp8", _i32, [_VP, _VP, ctypes.c_int64, ctypes.c_float, _VP]),
     ("ycx_decode", _i32, [ctypes.POINTER(DecodeDesc), _VP, _VP, _VP]),
     ("ycx_filter_decoded", _i32, [ctypes.POINTER(FilterDesc), _VP, _VP, _VP, _VP, _VP]),

@@ -232,6 +232,14 @@ def ibin_outputs(head, outs, input_hw):
     return z, xs
 
 
+def _require_detect_head(model):
+    """The detectors and predict decode boxes: a model that ends in a Classify head has none."""
+    from .nets.common import Classify
+    if isinstance(model.model[-1], Classify):
+        raise ValueError("ycx: this model's last layer is a Classify head ([N, c2] logits, no boxes to decode); "
+                         "call the Model itself")
+
+
 class DevicePost:
     """decode_box + non_max_suppression on device for fixed head shapes
     (``detect.py:29-144``): ycx_decode_filter -> ycx_sort_nms on the current
@@ -335,6 +343,7 @@ class Detector:
 
     def __init__(self, model, shape, device, anchors, anchors_mask, image_size=None, conf_thres=0.3,
                  nms_thres=0.3, max_det=300, use_graph=True, slot=None, fuse_heads=True, keep_heads=True):
+        _require_detect_head(model)
         self.model = model
         # a private engine unless the caller names a slot: the static buffers of one
         # Detector must never alias model(x)'s or another Detector's (in flight on
@@ -609,6 +618,7 @@ def predict(cfg_file, image_path=None, conf_threshold=0.3, nms_threshold=0.3, *,
     colors = colors_for(plan.num_labels)
     original = image if image is not None else read_image(image_path)
     net = prepare_model(plan, weights=weights, device=dev, precision=precision)
+    _require_detect_head(net)
     images = letterbox_gpu(original, target, device=dev).unsqueeze(0)  # detect.py:23-26 on the GPU
     with torch.no_grad():
         pred = net(images)

@@ -8,7 +8,8 @@ Lowering (once per input shape / device / precision):
    Bottleneck residual fused into the epilogue), stem conv (first conv on the
    fp32 NCHW image; ``stem_reorg`` when ReOrg precedes it: the space-to-depth is folded into
    that conv's operand gather), grouped conv, transposed conv (kernel == stride: ``deconv``), GhostConv's
-   depthwise 5x5 + concat with Ghost's shortcut (``ghost``), max-pool, upsample, concat, Detect/IDetect heads.
+   depthwise 5x5 + concat with Ghost's shortcut (``ghost``), max-pool, upsample, concat, Detect/IDetect heads,
+   the Classify head (``classify``: global average pool + the centre tap of its conv, ycx_classify).
 2. Passes: nearest-x2 upsample fused into its producing conv's store
    (YCX_OUT_NHWC_UP2); the SPPCSPC 5/9/13 pools run as a k5 cascade (exact for
    max with -inf padding); Contract, Expand and a Focus that reads an activation move their pixels with
@@ -36,7 +37,7 @@ from torch import nn
 from . import _lib as L
 from . import pack
 from .nets.common import (SP, SPP, SPPCSPC, SPPF, MP, Bottleneck, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC,
-                          Concat, Contract, Conv, DownC, Expand, Focus, Ghost, GhostConv, ReOrg, RepConv, Res,
+                          Classify, Concat, Contract, Conv, DownC, Expand, Focus, Ghost, GhostConv, ReOrg, RepConv, Res,
                           RobustConv, RobustConv2)
 from .nets.detect import Detect, IAuxDetect, IBin, IDetect
 from .pack import pack_deconv_weights, pack_fp8_weights  # noqa: F401  (re-exported)
@@ -131,6 +132,8 @@ DECONV_S = (2, 4, 8)
 DEPTH_GAIN = (2, 3, 4)
 DEPTH_RUN = 8
 DEPTH_NAME = {L.SD_CONTRACT: 'contract', L.SD_EXPAND: 'expand', L.SD_FOCUS: 'focus'}
+# what ycx_classify takes: a channel slice that is a multiple of CLASSIFY_RUN wide
+CLASSIFY_RUN = 8
 
 
 class Graph:
@@ -273,6 +276,29 @@ class Graph:
                                       f"{limits}")
         return self.add('depth', [x], out, mode=mode, gain=gain)
 
+    def classify(self, x: Val, w64, b64, k, s, p, groups):
+        """Classify (nets/common.py:815-825) as a node of its own kind, 'classify' (ycx_classify): the mean over
+        H x W, then the Conv2d on the 1 x 1 map. With an odd k and p == k // 2 only the centre tap meets data
+        and the output is 1 x 1 for any stride, so the node keeps w64[:, :, k//2, k//2] as a [cout][c][1][1]
+        weight. Its output is the model's: fp32 [n][cout], no buffer, no copy."""
+        if x.role in ('input', 'reorg'):
+            raise NotImplementedError("ycx: Classify on the model input (ycx_classify reads an NHWC activation, "
+                                      "not the image)")
+        if groups != 1 or k % 2 == 0 or p != k // 2:
+            raise NotImplementedError(f"ycx: Classify with k {k}, s {s}, p {p}, g {groups} has no HIP kernel: "
+                                      f"ycx_classify takes g == 1, an odd k and p == k // 2 (any s), where only the "
+                                      f"conv's centre tap meets the pooled 1 x 1 map")
+        cout, cin = int(w64.shape[0]), int(w64.shape[1])
+        if cin != x.c:
+            raise ValueError(f"ycx: Classify built for {cin} input channels reads a layer of {x.c} (the reference's "
+                             f"conv fails there)")
+        if x.c % CLASSIFY_RUN:
+            raise NotImplementedError(f"ycx: Classify on {x.c} channels has no HIP kernel: ycx_classify takes a "
+                                      f"channel slice that is a multiple of {CLASSIFY_RUN}")
+        w = w64[:, :, k // 2, k // 2].reshape(cout, cin, 1, 1).contiguous()
+        return self.add('classify', [x], Val(x.n, 1, 1, cout, role='output'), w=w, b=b64, k=1, s=1, p=0, ho=1, wo=1,
+                        kernel=k, stride=s)
+
     def upsample(self, x: Val):
         return self.add('up', [x], Val(x.n, 2 * x.h, 2 * x.w, x.c))
 
@@ -324,6 +350,15 @@ def focus_module(g: Graph, m: Focus, x: Val):
 
 def conv_or_ghost(g: Graph, m, x: Val):
     return ghostconv_module(g, m, x) if isinstance(m, GhostConv) else conv_module(g, m, x)
+
+
+def conv_or_rep(g: Graph, m, x: Val, residual=None):
+    """A block's cv2: a Conv, or in the Rep blocks a RepConv folded to its one 3x3 (``fold_repconv``), a
+    grouped one as a 'gconv' node within ycx_conv2d_grouped's limits."""
+    if not isinstance(m, RepConv):
+        return conv_module(g, m, x, residual=residual)
+    w, b = fold_repconv(m)
+    return g.conv(x, w, b, 3, m.stride, 1, act_of(m.act), residual=residual, groups=int(m.groups))
 
 
 def ghost_module(g: Graph, m: Ghost, x: Val):
@@ -433,7 +468,7 @@ def lower_module(g: Graph, m, x):
         return conv_module(g, m, x)
     if isinstance(m, RepConv):
         w, b = fold_repconv(m)
-        return g.conv(x, w, b, 3, m.stride, 1, act_of(m.act))
+        return g.conv(x, w, b, 3, m.stride, 1, act_of(m.act), groups=int(m.groups))
     if isinstance(m, nn.Conv2d):
         w = m.weight.detach().to('cpu', torch.float64)
         b = m.bias.detach().to('cpu', torch.float64) if m.bias is not None else torch.zeros(w.shape[0],
@@ -469,11 +504,13 @@ def lower_module(g: Graph, m, x):
         return g.upsample(x)
     if isinstance(m, nn.Identity):
         return x
-    if isinstance(m, Bottleneck):
+    if isinstance(m, Bottleneck):  # RepBottleneck too: its cv2 is a RepConv (nets/common.py:617-622)
         y = conv_module(g, m.cv1, x)
-        return conv_module(g, m.cv2, y, residual=x if m.add else None)
-    if isinstance(m, Res):  # ResX too (nets/common.py:212-230); the shortcut is cv3's epilogue residual
-        y = conv_module(g, m.cv2, conv_module(g, m.cv1, x))
+        return conv_or_rep(g, m.cv2, y, residual=x if m.add else None)
+    # ResX too (nets/common.py:212-230), and RepRes / RepResX, whose cv2 is a RepConv (:649-686); the shortcut is
+    # cv3's epilogue residual
+    if isinstance(m, Res):
+        y = conv_or_rep(g, m.cv2, conv_module(g, m.cv1, x))
         return conv_module(g, m.cv3, y, residual=x if m.add else None)
     if isinstance(m, RobustConv):  # nets/common.py:121-124; its channels_last call changes no value
         w, b = fold_robustconv(m)
@@ -487,6 +524,17 @@ def lower_module(g: Graph, m, x):
         return ghostconv_module(g, m, x)
     if isinstance(m, Ghost):
         return ghost_module(g, m, x)
+    if isinstance(m, Classify):
+        c = m.conv
+        if not isinstance(x, Val):
+            raise NotImplementedError("ycx: Classify reads one layer, got a list")
+        if _pair(c.dilation) != (1, 1):
+            raise NotImplementedError("ycx: dilated conv")
+        w = c.weight.detach().to('cpu', torch.float64)
+        b = c.bias.detach().to('cpu', torch.float64) if c.bias is not None else torch.zeros(w.shape[0],
+                                                                                            dtype=torch.float64)
+        return g.classify(x, w, b, _square(c.kernel_size, 'kernel'), _square(c.stride, 'stride'),
+                          _square(c.padding, 'padding'), int(c.groups))
     if isinstance(m, SPPCSPC):  # GhostSPPCSPC too: its cv1 .. cv7 are GhostConvs (nets/common.py:269-280)
         cv = conv_or_ghost
         x1 = cv(g, m.cv4, cv(g, m.cv3, cv(g, m.cv1, x)))
@@ -576,14 +624,17 @@ class Plan:
                                           f"only consumer; it has {len(v.consumers)} consumers")
         self.is_list = isinstance(x, list)
         self.out_vals = list(x) if self.is_list else [x]
+        for nd in g.nodes:  # a Classify's [n][c2] logits are the model's output, nothing reads them
+            if nd.kind == 'classify' and (nd.out is not x or nd.out.consumers):
+                raise NotImplementedError("ycx: Classify is lowered only as the model's last layer")
         self.graph = g
         self._eliminate_dead()
         self._passes()
 
     @property
     def conv_flops(self):
-        """Algorithmic FLOPs of the folded convs of every kind (``pack.flops``)."""
-        return sum(pack.flops(nd) for nd in self.graph.nodes if nd.kind in pack.CONV_KINDS)
+        """Algorithmic FLOPs of the folded convs of every kind and of a Classify head's dense layer (``pack.flops``)."""
+        return sum(pack.flops(nd) for nd in self.graph.nodes if nd.kind in pack.PACKED_KINDS)
 
     def counts(self):
         """Node kinds after the passes; 'conv' counts the original convs (a merged
@@ -821,6 +872,7 @@ class Engine:
             self.buffers.append(b.tensor)
         self.input_slots, self.output_slots, self.op_info = [], {}, []
         self._ksplit_ops = []  # (op index, workspace bytes) of the split-K convs
+        self.scratch = []  # per-op workspaces of their own (a classify node's pooled means)
         self.conv_flops = 0
         emit = {'stem2': lambda la: self._stem2_op(*la.nodes),
                 'conv_pair': lambda la: self._pair_op(*la.nodes, store_a=la.store_a),
@@ -829,6 +881,7 @@ class Engine:
                 'deconv': lambda la: self._plain_op(la.nodes[0], L.OP_DECONV, 'deconv_s{s}'),
                 'ghost': lambda la: self._plain_op(la.nodes[0], L.OP_GHOST, 'ghost_dw'),
                 'depth': lambda la: self._depth_op(la.nodes[0]),
+                'classify': lambda la: self._classify_op(la.nodes[0]),
                 'pool': lambda la: self._pool_op(la.nodes[0], levels=la.levels),
                 'copy': lambda la: self._copy_op(la.src, la.dst, la.off, la.scale, nchw=la.nchw)}
         ops = [emit[la.kind](la) for la in self.schedule.launches]
@@ -854,6 +907,20 @@ class Engine:
             return None
         return v.buf.tensor.data_ptr()
 
+    def _packed(self, node, bf16_weights=False, silu_ps=False):
+        """The node's packed weights and bias on the device (prepacked or ``pack.pack``), kept alive in
+        self.params and named in self.packed by graph position."""
+        i = 2 * self._conv_index[id(node)]
+        if self.prepacked is not None:
+            wt, bt = pack.take_prepacked(self.prepacked, i, pack.spec(node, self.precision, bf16_weights))
+        else:
+            wt, bt = pack.pack(node, self.precision, bf16_weights=bf16_weights, silu_ps=silu_ps,
+                               in_scale=self._scale(node.inputs[0]))
+        wt, bt = wt.to(self.device), bt.to(self.device)
+        self.params += [wt, bt]
+        self.packed[f"p{i}"], self.packed[f"p{i + 1}"] = wt, bt
+        return wt, bt
+
     def _conv_parts(self, node, bf16_weights=False, pool=None):
         """Packed weights/bias (prepacked or ``pack.pack``; on the device, kept alive in self.params and named
         in self.packed), the descriptor (``pack.desc``), the FLOPs and the op_info shape of a conv-kind node.
@@ -864,15 +931,7 @@ class Engine:
         # the fp32 parity plan keeps torch's silu(c) = c / (1 + e^-c)
         silu_ps = (node.kind in pack.DENSE and node.p['act'] == L.ACT_SILU and self.dt != L.DT_F32
                    and not _NO_SILU_PS)
-        i = 2 * self._conv_index[id(node)]
-        if self.prepacked is not None:
-            wt, bt = pack.take_prepacked(self.prepacked, i, pack.spec(node, self.precision, bf16_weights))
-        else:
-            wt, bt = pack.pack(node, self.precision, bf16_weights=bf16_weights, silu_ps=silu_ps,
-                               in_scale=self._scale(node.inputs[0]))
-        wt, bt = wt.to(self.device), bt.to(self.device)
-        self.params += [wt, bt]
-        self.packed[f"p{i}"], self.packed[f"p{i + 1}"] = wt, bt
+        wt, bt = self._packed(node, bf16_weights, silu_ps)
         d = pack.desc(node, self.precision, bf16_weights=bf16_weights, silu_ps=silu_ps, scales=self.scales, pool=pool)
         flops = pack.flops(node)
         self.conv_flops += flops
@@ -993,6 +1052,35 @@ class Engine:
                                  bytes=2 * x.n * x.h * x.w * x.c * self.dtype.itemsize))
         return op
 
+    def _classify_op(self, node):
+        """One OP_CLASSIFY (ycx_classify): the input slice's means into a workspace of the op's own, then the
+        centre-tap weights (fp32 in every precision) on them; the fp32 [n][cout] output is the model's. An fp8
+        plan reads e4m3 with the producer's scale and stores fp32, so the node has no scale of its own."""
+        x, out = node.inputs[0], node.out
+        wt, bt = self._packed(node)
+        d = L.ClassifyDesc()
+        d.n, d.h, d.w, d.c, d.in_c_off, d.in_c_stride = x.n, x.h, x.w, x.c, x.coff, x.buf.c
+        d.cout, d.dtype = out.c, self.dt
+        d.dequant = 1.0 / self._scale(x) if self.dt == L.DT_FP8 else 1.0
+        if d.in_c_off % CLASSIFY_RUN or d.in_c_stride % CLASSIFY_RUN:
+            raise NotImplementedError(f"ycx: Classify on the channel slice at {d.in_c_off} of {d.in_c_stride}: "
+                                      f"ycx_classify takes offsets and strides that are multiples of {CLASSIFY_RUN}")
+        ws = torch.empty((x.n, x.c), dtype=torch.float32, device=self.device)
+        self.scratch.append(ws)
+        op = L.Op()
+        op.kind = L.OP_CLASSIFY
+        op.d.classify = d
+        idx = len(self.op_info)
+        op.in_ = x.buf.tensor.data_ptr()
+        op.weight, op.bias, op.workspace = wt.data_ptr(), bt.data_ptr(), ws.data_ptr()
+        op.out = self._val_ptr(out, idx, 'out')
+        flops = pack.flops(node)
+        self.conv_flops += flops
+        nbytes = x.n * x.h * x.w * x.c * self.dtype.itemsize + 4 * (wt.numel() + bt.numel() + x.n * out.c)
+        self.op_info.append(dict(kind='classify', name='classify', flops=flops, bytes=nbytes,
+                                 shape=(x.n, x.h, x.w, x.c, out.c, 1, 1)))
+        return op
+
     def _copy_op(self, x, out, off, scale, nchw=False):
         d = L.CopyDesc()
         d.n, d.h, d.w, d.c, d.in_c_off, d.in_c_stride = x.n, x.h, x.w, x.c, x.coff, x.buf.c
@@ -1016,7 +1104,9 @@ class Engine:
 
     # ------------------------------------------------------------------
     def _alloc_outputs(self):
-        outs = [torch.empty((v.n, v.c, v.h, v.w), dtype=torch.float32, device=self.device) for v in self.out_vals]
+        # fp32 NCHW heads; a classify node's output is [n][c2] (Flatten, nets/common.py:825)
+        outs = [torch.empty((v.n, v.c) if v.producer.kind == 'classify' else (v.n, v.c, v.h, v.w),
+                            dtype=torch.float32, device=self.device) for v in self.out_vals]
         self._bind_outputs(outs)
         return outs
 
@@ -1208,6 +1298,8 @@ class Engine:
             return op.d.pool.ho
         if op.kind == L.OP_DEPTH:
             return op.d.depth.ho
+        if op.kind == L.OP_CLASSIFY:
+            return 1
         return op.d.copy.h * op.d.copy.scale
 
     def _exec_ops(self):

@@ -411,6 +411,101 @@ class RepConv(_Holder):
                                          nn.BatchNorm2d(num_features=c2))
 
 
+class RepBottleneck(Bottleneck):
+    """Bottleneck with cv2 a RepConv (nets/common.py:617-622). Like the reference it builds the parent with
+    shortcut=True, g=1, e=0.5 whatever it was given (so cv1 emits c2 / 2 channels and ``add`` ignores
+    ``shortcut``) and then sizes the RepConv from the ``e`` it was given: only e == 0.5 runs."""
+
+    def __init__(self, c1, c2, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, shortcut=True, g=1, e=0.5)
+        c_ = int(c2 * e)
+        self.cv2 = RepConv(c_, c2, 3, 1, g=g)
+
+
+class RepRes(Res):
+    """Res with cv2 a RepConv (nets/common.py:649-654)."""
+
+    def __init__(self, c1, c2, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.cv2 = RepConv(c_, c_, 3, 1, g=g)
+
+
+class RepResCSPA(ResCSPA):
+    """ResCSPA over RepRes blocks (nets/common.py:657-662)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*[RepRes(c_, c_, shortcut, g, e=0.5) for _ in range(n)])
+
+
+class RepResCSPB(ResCSPB):
+    """ResCSPB over RepRes blocks (nets/common.py:665-670)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=False, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2)
+        self.m = nn.Sequential(*[RepRes(c_, c_, shortcut, g, e=0.5) for _ in range(n)])
+
+
+class RepResCSPC(ResCSPC):
+    """ResCSPC over RepRes blocks (nets/common.py:673-678)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*[RepRes(c_, c_, shortcut, g, e=0.5) for _ in range(n)])
+
+
+class RepResX(ResX):
+    """ResX with cv2 a grouped RepConv, 32 groups by default (nets/common.py:681-686)."""
+
+    def __init__(self, c1, c2, shortcut=True, g=32, e=0.5):
+        super().__init__(c1, c2, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.cv2 = RepConv(c_, c_, 3, 1, g=g)
+
+
+class RepResXCSPA(ResXCSPA):
+    """ResXCSPA over RepResX blocks (nets/common.py:689-694)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=32, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*[RepResX(c_, c_, shortcut, g, e=0.5) for _ in range(n)])
+
+
+class RepResXCSPB(ResXCSPB):
+    """ResXCSPB over RepResX blocks (nets/common.py:697-702)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=False, g=32, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2)
+        self.m = nn.Sequential(*[RepResX(c_, c_, shortcut, g, e=0.5) for _ in range(n)])
+
+
+class RepResXCSPC(ResXCSPC):
+    """ResXCSPC over RepResX blocks (nets/common.py:705-710)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=32, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*[RepResX(c_, c_, shortcut, g, e=0.5) for _ in range(n)])
+
+
+class Classify(_Holder):
+    """Classification head, x(b, c1, h, w) -> (b, c2): AdaptiveAvgPool2d(1), a biased Conv2d(c1, c2, k, s,
+    autopad(k, p), groups=g) on the 1 x 1 map, Flatten (nets/common.py:815-825). The engine runs the pool
+    and the conv's centre tap as one ycx_classify op."""
+
+    def __init__(self, c1, c2, k=1, s=1, p=None, g=1):
+        super().__init__()
+        self.aap = nn.AdaptiveAvgPool2d(1)
+        self.conv = nn.Conv2d(c1, c2, k, s, autopad(k, p), groups=g)
+        self.flat = nn.Flatten()
+
+
 class SPPF(_Holder):
     """cv2(cat[x, m x, m m x, m m m x]) with k=5 (nets/common.py:771-784)."""
 

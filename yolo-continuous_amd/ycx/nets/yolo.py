@@ -26,9 +26,10 @@ from torch import nn
 
 from ..utils.helper_io import cvt_cfg
 from .common import (SP, SPP, SPPCSPC, SPPF, MP, Bottleneck, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC,
-                     Concat, Contract, Conv, DownC, Expand, Focus, Ghost, GhostConv, GhostCSPA, GhostCSPB, GhostCSPC,
-                     GhostSPPCSPC, ImplicitA, ImplicitM, ReOrg, RepConv, Res, ResCSPA, ResCSPB, ResCSPC, ResX, ResXCSPA,
-                     ResXCSPB, ResXCSPC, RobustConv, RobustConv2, dw_conv)
+                     Classify, Concat, Contract, Conv, DownC, Expand, Focus, Ghost, GhostConv, GhostCSPA, GhostCSPB,
+                     GhostCSPC, GhostSPPCSPC, ImplicitA, ImplicitM, ReOrg, RepBottleneck, RepConv, RepRes, RepResCSPA,
+                     RepResCSPB, RepResCSPC, RepResX, RepResXCSPA, RepResXCSPB, RepResXCSPC, Res, ResCSPA, ResCSPB,
+                     ResCSPC, ResX, ResXCSPA, ResXCSPB, ResXCSPC, RobustConv, RobustConv2, dw_conv)
 from .detect import Detect, IAuxDetect, IBin, IDetect
 
 
@@ -51,24 +52,32 @@ _MODULES = {
     'GhostConv': GhostConv, 'Ghost': Ghost, 'GhostCSPA': GhostCSPA, 'GhostCSPB': GhostCSPB, 'GhostCSPC': GhostCSPC,
     'GhostSPPCSPC': GhostSPPCSPC,
     'Focus': Focus, 'Contract': Contract, 'Expand': Expand,
+    'RepBottleneck': RepBottleneck, 'RepRes': RepRes, 'RepResX': RepResX,
+    'RepResCSPA': RepResCSPA, 'RepResCSPB': RepResCSPB, 'RepResCSPC': RepResCSPC,
+    'RepResXCSPA': RepResXCSPA, 'RepResXCSPB': RepResXCSPB, 'RepResXCSPC': RepResXCSPC,
+    'Classify': Classify,
 }
 # Reference modules constructible by its parse_model but used by neither shipped
 # YAML: named here so the error says "out of scope", not "unknown".
+# RepBottleneckCSPA/B/C: the reference's own forward fails (they build RepBottleneck(c_, c_, ..., e=1.0), whose
+# cv1 emits c_ / 2 channels into a RepConv sized for c_), so there is no behaviour to match.
 _OUT_OF_SCOPE = {
     'Chuncat', 'Shortcut', 'Foldcut', 'Stem',
-    'GhostStem', 'Classify',
-    'TransformerLayer', 'TransformerBlock', 'RepBottleneck',
-} | {f'{p}{s}' for p in ('RepRes', 'RepResX', 'RepBottleneck')
-     for s in ('CSPA', 'CSPB', 'CSPC')}
+    'GhostStem',
+    'TransformerLayer', 'TransformerBlock',
+    'RepBottleneckCSPA', 'RepBottleneckCSPB', 'RepBottleneckCSPC',
+}
 # The Ghost family runs on ycx_ghost_dw, which reads an NHWC activation: none of them can take the
 # fp32 NCHW image (like "grouped conv on the model input"), so there they stay out of scope.
 _GHOST_LIKE = (GhostConv, Ghost, GhostCSPA, GhostCSPB, GhostCSPC, GhostSPPCSPC)
 
 _CONV_LIKE = (nn.Conv2d, Conv, RobustConv, RobustConv2, dw_conv, RepConv, DownC, SPP, SPPF, SPPCSPC, Bottleneck,
               BottleneckCSPA, BottleneckCSPB, BottleneckCSPC, Res, ResCSPA, ResCSPB, ResCSPC, ResX, ResXCSPA, ResXCSPB,
-              ResXCSPC, GhostConv, Ghost, GhostCSPA, GhostCSPB, GhostCSPC, GhostSPPCSPC, Focus)
+              ResXCSPC, GhostConv, Ghost, GhostCSPA, GhostCSPB, GhostCSPC, GhostSPPCSPC, Focus, RepBottleneck, RepRes,
+              RepResCSPA, RepResCSPB, RepResCSPC, RepResX, RepResXCSPA, RepResXCSPB, RepResXCSPC)
 _CSP_LIKE = (DownC, SPPCSPC, BottleneckCSPA, BottleneckCSPB, BottleneckCSPC, ResCSPA, ResCSPB, ResCSPC, ResXCSPA,
-             ResXCSPB, ResXCSPC, GhostCSPA, GhostCSPB, GhostCSPC, GhostSPPCSPC)
+             ResXCSPB, ResXCSPC, GhostCSPA, GhostCSPB, GhostCSPC, GhostSPPCSPC, RepResCSPA, RepResCSPB, RepResCSPC,
+             RepResXCSPA, RepResXCSPB, RepResXCSPC)
 _ACTS = {'LeakyReLU': nn.LeakyReLU, 'SiLU': nn.SiLU, 'Identity': nn.Identity}
 _CALL_RE = re.compile(r'^(?:nn\.)?(\w+)\((.*)\)$')
 
@@ -139,6 +148,11 @@ def parse_model(d, ch, anchors, num_classes):
             c2 = ch[f] * args[0] ** 2
         elif m is Expand:
             c2 = ch[f] // args[0] ** 2
+        elif m is Classify:  # no special case in the reference: the args as written (c1 explicit, unscaled), c2 = ch[f]
+            if not isinstance(f, int):
+                raise NotImplementedError(f"ycx: Classify reads one layer, got from={f} (the reference's parser "
+                                          f"fails on a list there)")
+            c2 = ch[f]
         else:
             c2 = ch[f]
         m_ = nn.Sequential(*[m(*args) for _ in range(n)]) if n > 1 else m(*args)
@@ -173,7 +187,8 @@ class Model(nn.Module):
     """Drop-in for nets/yolo.py ``Model`` (constructor :95-112, forward :143-153).
 
     forward(x: fp32 [N, C, H, W] on a ROCm device) -> the last layer's output:
-    ``[P5, P4, P3]`` fp32 NCHW logits for a Detect head (nets/detect.py:38).
+    ``[P5, P4, P3]`` fp32 NCHW logits for a Detect head (nets/detect.py:38), one fp32
+    ``[N, c2]`` tensor for a Classify head (nets/common.py:815-825).
     ``precision`` selects the kernel dtype: 'fp16' (default: IEEE half
     activations and weights on the f16 MFMA, fp32 accumulate -- the bf16 kernels
     at the bf16 rate with an 11-bit significand, the mode that holds north_star's

@@ -12,26 +12,30 @@ Packed layouts (``spec``; bias fp32 [cout_pad] unless noted):
   stem, stem_reorg     [kh][kw][cin][cout_pad] fp32
   gconv, ghost         [kh][kw][cout][cin_g] fp32, bias [cout] (ghost: cout = the hidden width c, cin_g 1)
   deconv               [s*s][cout][cin] in the activation dtype, bias [cout]
+  classify             [cout][c] fp32 in every precision: the centre tap of Classify's conv, bias [cout]
 
 SiLU epilogues of the 16-bit / fp8 plans run on c' = -log2(e) c (YCX_ACT_SILU_PS): with ``silu_ps`` a dense
 conv's weights and bias are scaled in float64 before their one rounding (fp8: the fp32 bias and dq rows,
-so the e4m3 weights are unchanged). gconv, ghost and deconv are never pre-scaled."""
+so the e4m3 weights are unchanged). gconv, ghost, deconv and classify are never pre-scaled. A classify node
+has no ycx_conv_desc (``desc`` is not for it): the engine fills its ycx_classify_desc."""
 import torch
 
 from . import _lib as L
 from .schedule import cout_pad
 
 CONV_KINDS = ('conv', 'stem', 'stem_reorg', 'gconv', 'deconv', 'ghost')
+PACKED_KINDS = CONV_KINDS + ('classify',)  # every kind with packed tensors: the convs and the Classify head's dense layer
 DENSE = ('conv', 'stem', 'stem_reorg')  # the kinds with padded output rows, a SiLU pre-scale and an fp8 path
 DTYPE = {'bf16': torch.bfloat16, 'f32': torch.float32, 'fp8': torch.float8_e4m3fn, 'fp16': torch.float16}
 DT = {'bf16': L.DT_BF16, 'f32': L.DT_F32, 'fp8': L.DT_FP8, 'fp16': L.DT_F16}
 
 
 def conv_index(nodes):
-    """{id(node): i} over the conv-kind nodes in graph order: node i packs into tensors p<2i>, p<2i+1>.
+    """{id(node): i} over the nodes with packed tensors (``PACKED_KINDS``) in graph order: node i packs into
+    tensors p<2i>, p<2i+1>.
     Named by position in the graph, not by packing order: which convs fuse (stem pair, 1x1 pair) varies
     with the batch size and the A/B switches, and a prepack file is reused at any batch size."""
-    return {id(nd): i for i, nd in enumerate(nd for nd in nodes if nd.kind in CONV_KINDS)}
+    return {id(nd): i for i, nd in enumerate(nd for nd in nodes if nd.kind in PACKED_KINDS)}
 
 
 def pack_fp8_weights(wp):
@@ -65,6 +69,8 @@ def spec(node, precision, bf16_weights=False):
         return (k, k, d0, d1), torch.float32, (d0,)
     if node.kind == 'deconv':            # w [cin][cout][s][s]
         return (k * k, d1, d0), DTYPE[precision], (d1,)
+    if node.kind == 'classify':          # w [cout][c][1][1], the centre tap
+        return (d0, d1), torch.float32, (d0,)
     stem = node.kind != 'conv'           # w [cout][cin][k][k]
     cpad = cout_pad(precision, d0, stem or bf16_weights)
     if stem:
@@ -84,6 +90,8 @@ def pack(node, precision, *, bf16_weights=False, silu_ps, in_scale=1.0):
     assert node.kind in DENSE or not silu_ps
     if node.kind in ('gconv', 'ghost'):
         return w64.permute(2, 3, 0, 1).contiguous().to(torch.float32), b64.to(torch.float32)
+    if node.kind == 'classify':
+        return w64.reshape(w64.shape[0], w64.shape[1]).contiguous().to(torch.float32), b64.to(torch.float32)
     wshape, wdt, _ = spec(node, precision, bf16_weights)
     if node.kind == 'deconv':
         return pack_deconv_weights(w64, wdt), b64.to(torch.float32)
@@ -124,7 +132,8 @@ def scale_of(scales, v):
 
 
 def desc(node, precision, *, bf16_weights=False, silu_ps, scales, pool=None):
-    """The ycx_conv_desc of a conv-kind node, ``tile`` and ``k_split`` left 0 for the engine to pick.
+    """The ycx_conv_desc of a conv-kind node (not a classify node), ``tile`` and ``k_split`` left 0 for the
+    engine to pick.
     node.p carries kernel, stride, pad and groups for every kind (a deconv's k == s, a ghost's 5 / 1 / 2 and
     groups = c), the input and output values carry cin and cout (a ghost's c and 2c); what is left to tell
     apart is cout_pad, the input slice and the fp8 scales.
@@ -163,7 +172,8 @@ def desc(node, precision, *, bf16_weights=False, silu_ps, scales, pool=None):
 def flops(node):
     """Algorithmic FLOPs of a conv-kind node: 2*N*Ho*Wo*Cout*Cin*k*k (a grouped conv: Cin = cin_g, the
     second dim of its weights; a ghost node: its depthwise 5x5, 2*N*H*W*c*25); a transposed conv
-    2*N*H*W*Cin*s*s*Cout: each input pixel feeds an s x s block (weights [cin][cout][s][s], k == s)."""
+    2*N*H*W*Cin*s*s*Cout: each input pixel feeds an s x s block (weights [cin][cout][s][s], k == s); a classify
+    node: its dense layer, 2*N*Cout*C (k 1 on a 1 x 1 map)."""
     x, p = node.inputs[0], node.p
     px = x.h * x.w if node.kind == 'deconv' else p['ho'] * p['wo']
     return 2 * x.n * px * int(p['w'].shape[0]) * int(p['w'].shape[1]) * p['k'] ** 2

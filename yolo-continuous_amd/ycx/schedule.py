@@ -29,6 +29,7 @@ class Launch:
     deconv     nodes (deconv,)
     ghost      nodes (ghost,)
     depth      nodes (depth,): one ycx_space_depth move (Contract, Expand, Focus on an activation)
+    classify   nodes (classify,): one ycx_classify (global average pool + the Classify head's dense layer)
     pool       nodes: the cascade's pools, ``levels`` of them
     copy       nodes (up | concat | tonchw,): ``src`` -> channels from ``off`` of ``dst``, upsampled
                by ``scale`` (1 or 2), ``nchw``: to the fp32 NCHW output
@@ -251,7 +252,7 @@ class Schedule:
                 add('conv_pair', nd, pairs[i], *trio, store_a=len(nd.out.consumers) > 1 and not trio)
             elif k in ('conv', 'stem', 'stem_reorg'):
                 add('conv', nd, *([pooled[i]] if i in pooled else []))
-            elif k in ('gconv', 'deconv', 'ghost', 'depth'):
+            elif k in ('gconv', 'deconv', 'ghost', 'depth', 'classify'):
                 add(k, nd)
             elif k == 'pool':
                 chain = cascades.get(i, [nd])
